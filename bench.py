@@ -19,11 +19,15 @@ from rank 0 (dist.pack / broadcast / unpack_conditioning; RCCL over xGMI, SURVEY
 path; barrier + synchronize bracket the timed region, MAX over ranks (dist.max_over_ranks).  tests/test_dist_cpu.py drives
 exactly those functions with 2 gloo ranks.
 
-Besides the headline the line carries: per-stage times of one batch on all CUs (`stages_ms`), the other single-GPU BASELINE
-configs (`c2_flow_only`, `c3_hift_only` with HBM- and MFMA-roofline fractions, exact-f32 beside bf16x3 products), three
-roofline blocks (`roofline` = the by-time dominant kernel of the pipeline, the flow's flash attention; `roofline_flow` = the
-flow stage on SURVEY §8d's 4.937 TF per utterance; `roofline_decode` = the decode step at step level, 727.6 MB per step, and
-its largest weight stream), and `cpu_baseline` (oracle, median of 3 warmed samples per component).
+A plain run sets up, warms up, times the K steps and prints the headline line (`ms_per_step` = the timed region / K).
+`--dump-outputs DIR` writes what the last timed step returned to its caller, the (8, 240 000) float32 waveforms of that
+pass, as DIR/wav.npy (DIR/wav_rank<r>.npy on the other ranks): the inputs are seeded, so two builds compare output for output.
+With `--full` the line also carries: the batch-1 latency (`config.batch1`), per-stage times of one batch on all CUs
+(`stages_ms`), the other single-GPU BASELINE configs (`c2_flow_only`, `c3_hift_only` with HBM- and MFMA-roofline fractions,
+exact-f32 beside bf16x3 products), three roofline blocks (`roofline` = the by-time dominant kernel of the pipeline, the flow's
+flash attention; `roofline_flow` = the flow stage on SURVEY §8d's 4.937 TF per utterance; `roofline_decode` = the decode step
+at step level, 727.6 MB per step, and its largest weight stream), and `cpu_baseline` (oracle, median of 3 warmed samples per
+component).
 """
 import argparse
 import json
@@ -171,8 +175,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=32)   # 32 pipelined passes (~5 s): fill + drain (~0.5 s) stay inside the timed region
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the stage / C2 / C3 measurements (tuning runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure batch-1 latency, stage times, C1 / C2 / C3, the rooflines and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the waveforms of the last timed step to DIR/wav.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the stage / C1 / C2 / C3 measurements")
     ap.add_argument("--flow-dtype", default="fp16", choices=["fp16", "bf16"])
     ap.add_argument("--llm-dtype", default="fp16", choices=["fp16", "bf16"],
                     help="16-bit operand type of the LLM (fp32 accumulate).  fp16 = what the reference's fp16 flag gives (llm.half(), cli/model.py:43-45) and "
@@ -189,6 +197,8 @@ def main():
     ap.add_argument("--llm-loops", type=int, default=2,
                     help="concurrent decode loops (one utterance batch each, own KV caches) on the decode CUs")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     torch.set_num_threads(min(16, torch.get_num_threads()))  # CPU share per GPU on the box; keeps 8 ranks from oversubscribing
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -309,9 +319,14 @@ def main():
     fence()
     model.pipeline_stats = [] if os.environ.get("CV_PIPELINE_STATS") else None
     t0 = time.perf_counter()
-    run_steps(args.steps)
+    last = run_steps(args.steps)
     fence()
     elapsed = cd.max_over_ranks(time.perf_counter() - t0, dev, dist)
+    if args.dump_outputs:   # 8 x 240 000 float32 = 7.7 MB per rank
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "wav.npy" if rank == 0 else f"wav_rank{rank}.npy"),
+                last.to(torch.float32).numpy())
     if model.pipeline_stats:
         for kind in ("llm", "flow"):
             js = [(e - s_) * 1e3 / n for k, n, s_, e in model.pipeline_stats if k == kind]
@@ -331,26 +346,6 @@ def main():
 
     out = None
     if rank == 0:
-        one = make_batch(local=True)
-        # ---- batch-1 latency of the same pipeline (BASELINE metric: "batch 1 and 8"; north_star target RTF < 0.05)
-        def run1():
-            return model.tts_batch(one["texts"][:1], one["prompt_texts"][:1], one["llm_prompt_speech_tokens"][:1],
-                                   one["flow_prompt_speech_tokens"][:1], one["prompt_speech_feats"][:1], one["flow_embeddings"][:1],
-                                   forced=forced_m[:1], to_host=True)
-        for _ in range(2):
-            run1()
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        n1 = 3
-        for _ in range(n1):
-            run1()
-        torch.cuda.synchronize()
-        lat = (time.perf_counter() - t1) / n1
-        b1 = {"latency_ms": round(lat * 1e3, 2), "rtf": round(lat / AUDIO_S_PER_UTT, 5), "audio_s_per_s": round(AUDIO_S_PER_UTT / lat, 2)}
-
-        extras = {}
-        if not args.no_extras:
-            extras = measure_extras(model, llm, flow, hift, lc, fc, hc, one, forced_m, fdt, args)
         replay = ("each decode step is ONE captured hipGraph, replayed node by node (hipLaunchKernel per captured kernel) on CU-masked "
                   "streams because hipGraph replays ignore a stream's CU mask" if args.llm_cu_slots else
                   "each decode step is ONE captured hipGraph replayed with hipGraphLaunch")
@@ -366,13 +361,31 @@ def main():
                                    "(prefill 282, N_g 250, flow T 1000 x 10 CFG Euler steps, HiFT 500 frames); token loop: " + replay,
                        "utterances_per_gpu": B, "rtf": round(elapsed / audio_s, 6), "parallelism": f"utterance-parallel x{world}",
                        "llm_cu_slots_per_xcd": args.llm_cu_slots, "llm_decode_loops": args.llm_loops, "batches_per_decode_loop": args.llm_merge, "batches_per_flow_pass": args.flow_merge,
-                       "flow_fused_tblock": bool(flow.decoder.estimator.fused), "batch1": b1, "dist": dist_info},
+                       "flow_fused_tblock": bool(flow.decoder.estimator.fused), "dist": dist_info},
         }
-        out.update(extras)
-        if "roofline" not in out:
-            out["roofline"] = measure_decode_roofline(llm, lc, rows=min(llm.max_batch, UTT_PER_GPU * max(1, args.llm_merge)))
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(lsd, fsd, hsd, lc, fc, hc)
+        if args.full:
+            one = make_batch(local=True)
+            # ---- batch-1 latency of the same pipeline (BASELINE metric: "batch 1 and 8"; north_star target RTF < 0.05)
+            def run1():
+                return model.tts_batch(one["texts"][:1], one["prompt_texts"][:1], one["llm_prompt_speech_tokens"][:1],
+                                       one["flow_prompt_speech_tokens"][:1], one["prompt_speech_feats"][:1], one["flow_embeddings"][:1],
+                                       forced=forced_m[:1], to_host=True)
+            for _ in range(2):
+                run1()
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            n1 = 3
+            for _ in range(n1):
+                run1()
+            torch.cuda.synchronize()
+            lat = (time.perf_counter() - t1) / n1
+            out["config"]["batch1"] = {"latency_ms": round(lat * 1e3, 2), "rtf": round(lat / AUDIO_S_PER_UTT, 5), "audio_s_per_s": round(AUDIO_S_PER_UTT / lat, 2)}
+            if not args.no_extras:
+                out.update(measure_extras(model, llm, flow, hift, lc, fc, hc, one, forced_m, fdt, args))
+            if "roofline" not in out:
+                out["roofline"] = measure_decode_roofline(llm, lc, rows=min(llm.max_batch, UTT_PER_GPU * max(1, args.llm_merge)))
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(lsd, fsd, hsd, lc, fc, hc)
         print(json.dumps(out), flush=True)
     fence()
     model.close()
