@@ -143,6 +143,25 @@ class SampleParams(C.Structure):
     ]
 
 
+class SpkConvParams(C.Structure):
+    _fields_ = [
+        ("B", _i32), ("T_in", _i32), ("F_in", _i32), ("cin", _i32),
+        ("x", _vp), ("x_bs", _i64), ("ldx", _i32),
+        ("in_len", _vp),
+        ("kf", _i32), ("kt", _i32), ("sf", _i32), ("st", _i32), ("dt", _i32), ("pf", _i32), ("pt", _i32),
+        ("pre_scale", _vp), ("pre_shift", _vp),
+        ("w", _vp), ("ldw", _i32),
+        ("N", _i32), ("T_out", _i32), ("F_out", _i32),
+        ("bias", _vp),
+        ("res", _vp), ("res_bs", _i64), ("ldres", _i32),
+        ("relu", _i32),
+        ("gate", _vp), ("gate_bs", _i64), ("gate_seg", _i32),
+        ("y", _vp), ("y_bs", _i64), ("ldy", _i32),
+        ("out_len", _vp),
+        ("psum", _vp), ("psum_bs", _i64),
+    ]
+
+
 class LlmLayer(C.Structure):
     _fields_ = [("p_qkv", _vp), ("bqkv", _vp), ("p_o", _vp), ("p_gu", _vp), ("p_down", _vp), ("g_in", _vp), ("kcache", _vp), ("vtcache", _vp)]
 
@@ -232,7 +251,8 @@ def lib():
         _lib = C.CDLL(LIB_PATH)
         _lib.cv_arch.restype = C.c_char_p
         for name, st in (("gemm", GemmParams), ("norm", NormParams), ("attn", AttnParams), ("skinny", SkinnyParams),
-                         ("sample", SampleParams), ("groupnorm", GroupNormParams), ("tblock", TBlockParams), ("resblock", ResblockParams)):
+                         ("sample", SampleParams), ("groupnorm", GroupNormParams), ("tblock", TBlockParams), ("resblock", ResblockParams),
+                         ("spk_conv", SpkConvParams)):
             fn = getattr(_lib, f"cv_sizeof_{name}_params")
             if fn() != C.sizeof(st):
                 raise RuntimeError(f"ABI mismatch for cv_{name}_params: C {fn()} vs ctypes {C.sizeof(st)}")
@@ -259,7 +279,8 @@ EXPORTS = ["cv_version", "cv_arch", "cv_gemm", "cv_layernorm", "cv_attention",
            "cv_sizeof_flow_solver_desc", "cv_sizeof_flow_block", "cv_sizeof_flow_tblock", "cv_flow_euler_enqueue",
            "cv_flow_euler_graph_create", "cv_flow_euler_graph_launch", "cv_flow_euler_graph_destroy",
            "cv_sizeof_hift_decode_desc", "cv_sizeof_hift_stage", "cv_sizeof_hift_resunit", "cv_hift_decode_enqueue", "cv_hift_decode",
-           "cv_hift_decode_graph_create"]
+           "cv_hift_decode_graph_create", "cv_spk_power", "cv_spk_log_cmn", "cv_sizeof_spk_conv_params", "cv_spk_conv",
+           "cv_spk_cam_gate", "cv_spk_stats_pool"]
 
 TORCH_DT = {torch.float32: CV_F32, torch.bfloat16: CV_BF16, torch.float16: CV_F16}
 DT_TORCH = {v: k for k, v in TORCH_DT.items()}

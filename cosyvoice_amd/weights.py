@@ -465,3 +465,76 @@ def flow_v1_specs(cfg) -> List[Spec]:
 
 def flow_v1_state_dict(cfg, seed: int = 1986, round_to=None):
     return materialize(flow_v1_specs(cfg), seed, round_to)
+
+
+# --------------------------------------------------------------------------- CAM++ speaker encoder
+# CAMPPlus(feat_dim=80, embedding_size=192) (speaker/speaker_encoder.py:154-159; module tree speaker/CAMPPlus.py:214-451).
+CAMPPLUS_BLOCKS = ((12, 1), (24, 2), (16, 2))   # (layers, dilation) of block1..3; growth 32, bottleneck 128, k3
+CAMPPLUS_EMBED = 192
+
+
+def _campplus_bn(specs, name, ch, affine=True):
+    """BatchNorm with running statistics: gain 1 + N(0, 0.1), bias and running_mean N(0, 0.1), running_var U(0.5, 1.5)."""
+    if affine:
+        specs.append((f"{name}.weight", (ch,), "norm_w", 0.1))
+        specs.append((f"{name}.bias", (ch,), "normal", 0.1))
+    specs.append((f"{name}.running_mean", (ch,), "normal", 0.1))
+    specs.append((f"{name}.running_var", (ch,), "alpha", 0.0))
+    specs.append((f"{name}.num_batches_tracked", (), "count", 0.0))
+
+
+def _campplus_conv2d(specs, name, cout, cin, k):
+    # nn.Conv2d's own initialiser: kaiming_uniform_(a=sqrt(5)) = U(+-1/sqrt(fan_in))
+    specs.append((name, (cout, cin, k, k), "uniform", 1.0 / math.sqrt(cin * k * k)))
+
+
+def _campplus_conv1d(specs, name, cout, cin, k, bias=False):
+    # CAMPPlus.__init__ re-initialises every Conv1d: kaiming_normal_ (std sqrt(2 / fan_in)); biases drawn small instead of zero
+    specs.append((f"{name}.weight", (cout, cin, k), "normal", math.sqrt(2.0 / (cin * k))))
+    if bias:
+        specs.append((f"{name}.bias", (cout,), "normal", 0.1))
+
+
+def campplus_specs() -> List[Spec]:
+    s: List[Spec] = []
+    _campplus_conv2d(s, "head.conv1.weight", 32, 1, 3)
+    _campplus_bn(s, "head.bn1", 32)
+    for layer in ("layer1", "layer2"):
+        for i in (0, 1):
+            p = f"head.{layer}.{i}"
+            _campplus_conv2d(s, f"{p}.conv1.weight", 32, 32, 3)
+            _campplus_bn(s, f"{p}.bn1", 32)
+            _campplus_conv2d(s, f"{p}.conv2.weight", 32, 32, 3)
+            _campplus_bn(s, f"{p}.bn2", 32)
+            if i == 0:
+                _campplus_conv2d(s, f"{p}.shortcut.0.weight", 32, 32, 1)
+                _campplus_bn(s, f"{p}.shortcut.1", 32)
+    _campplus_conv2d(s, "head.conv2.weight", 32, 32, 3)
+    _campplus_bn(s, "head.bn2", 32)
+    _campplus_conv1d(s, "xvector.tdnn.linear", 128, 320, 5)
+    _campplus_bn(s, "xvector.tdnn.nonlinear.batchnorm", 128)
+    ch = 128
+    for bi, (n, _) in enumerate(CAMPPLUS_BLOCKS, 1):
+        for i in range(n):
+            p = f"xvector.block{bi}.tdnnd{i + 1}"
+            _campplus_bn(s, f"{p}.nonlinear1.batchnorm", ch + 32 * i)
+            _campplus_conv1d(s, f"{p}.linear1", 128, ch + 32 * i, 1)
+            _campplus_bn(s, f"{p}.nonlinear2.batchnorm", 128)
+            _campplus_conv1d(s, f"{p}.cam_layer.linear_local", 32, 128, 3)
+            _campplus_conv1d(s, f"{p}.cam_layer.linear1", 64, 128, 1, bias=True)
+            _campplus_conv1d(s, f"{p}.cam_layer.linear2", 32, 64, 1, bias=True)
+        ch += 32 * n
+        _campplus_bn(s, f"xvector.transit{bi}.nonlinear.batchnorm", ch)
+        _campplus_conv1d(s, f"xvector.transit{bi}.linear", ch // 2, ch, 1)
+        ch //= 2
+    _campplus_bn(s, "xvector.out_nonlinear.batchnorm", ch)
+    _campplus_conv1d(s, "xvector.dense.linear", CAMPPLUS_EMBED, 2 * ch, 1)
+    _campplus_bn(s, "xvector.dense.nonlinear.batchnorm", CAMPPLUS_EMBED, affine=False)
+    return s
+
+
+def campplus_state_dict(seed: int = 1986) -> Dict[str, torch.Tensor]:
+    """Key-seeded CAM++ weights in the reference module's key order (num_batches_tracked = 0, int64)."""
+    specs = campplus_specs()
+    sd = materialize([sp for sp in specs if sp[2] != "count"], seed)
+    return {k: (torch.zeros(shape, dtype=torch.int64) if kind == "count" else sd[k]) for k, shape, kind, _ in specs}

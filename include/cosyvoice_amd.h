@@ -265,6 +265,55 @@ int cv_stft_magnitude(const float* spec, int32_t ld_spec, float* mag, int32_t ld
 int cv_log_clamp_channels_first(const float* mel, int32_t ld, float* out, int32_t B, int32_t T, int32_t n_mels, float clip, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Speaker embedding: CosyVoiceFrontEnd._extract_spk_embedding (cosyvoice/cli/frontend.py:91-100) = Kaldi fbank (16 kHz, 80 bins,
+ * dither 0) - per-bin mean, then CAM++ (cosyvoice/speaker/CAMPPlus.py:384-451, feat_dim 80, embedding 192).  The fbank's DFT
+ * (frames x a cos/sin basis with DC removal, pre-emphasis and the Povey window folded in) and its mel projection are cv_gemm
+ * calls.  Ragged batches: `len` / `in_len` / `out_len` are per-sequence int32 lengths on the device; reads and reductions
+ * stop at a sequence's own length and rows at or past it are written as 0, so a batch row is bit-identical to that sequence
+ * run alone.  No atomics.
+ * ------------------------------------------------------------------------------------------ */
+/* spec [rows][ld_spec] = [re(nbins) | im(nbins) | ...] -> pw [rows][ld_pow] = re^2 + im^2 (columns >= nbins untouched) */
+int cv_spk_power(const float* spec, int32_t ld_spec, float* pw, int32_t ld_pow, int32_t rows, int32_t nbins, void* stream);
+/* mel [B][T][ld_mel] -> out [B][T][ldo] = log(max(mel, FLT_EPSILON)), minus its mean over frames t < len[b] when cmn != 0;
+ * frames t >= len[b] = 0.  n_mels <= 256. */
+int cv_spk_log_cmn(const float* mel, int32_t ld_mel, const int32_t* len, int32_t B, int32_t T, int32_t n_mels, int32_t cmn,
+                   float* out, int32_t ldo, void* stream);
+/* cv_spk_conv — every Conv2d / Conv1d of CAM++ as one implicit-GEMM kernel (exact-f32 MFMA, fp32 accumulate):
+ *   y[b][t][f][n] = epilogue( sum_{i_f, i_t, ci} A(b, t*st + i_t*dt - pt, f*sf + i_f - pf, ci) * w[n][(i_f*kt + i_t)*cin + ci] )
+ * x rows are (time, frequency) pairs: x[b*x_bs + (t*F_in + f)*ldx + ci]; taps outside [0, in_len[b]) x [0, F_in) read 0.
+ * Prologue (pre_scale != NULL): A = relu(x * pre_scale[ci] + pre_shift[ci]) — a BatchNorm -> ReLU that precedes the conv.
+ * Epilogue: v = acc + bias[n] + res[row][n]; relu; v *= gate[b][t / gate_seg][n] (gate pitch N per segment); rows
+ * t >= out_len[b] = 0; psum (F_out == 1): psum[b][g][n] = sum of output rows 4g..4g+3 (the CAM gate's input).
+ * Limits: N % 32 == 0; cin == 1 with kf*kt <= 16, or cin % 16 == 0 with 16-byte aligned x rows; ldw % 16 == 0, w 16-byte aligned. */
+typedef struct cv_spk_conv_params {
+  int32_t B, T_in, F_in, cin;
+  const float* x; int64_t x_bs; int32_t ldx;
+  const int32_t* in_len;                      /* [B] or NULL (= T_in) */
+  int32_t kf, kt, sf, st, dt, pf, pt;         /* taps, strides, time dilation, paddings (frequency, time) */
+  const float* pre_scale; const float* pre_shift;
+  const float* w; int32_t ldw;
+  int32_t N, T_out, F_out;
+  const float* bias;
+  const float* res; int64_t res_bs; int32_t ldres;
+  int32_t relu;
+  const float* gate; int64_t gate_bs; int32_t gate_seg;
+  float* y; int64_t y_bs; int32_t ldy;
+  const int32_t* out_len;                     /* [B] or NULL (= T_out) */
+  float* psum; int64_t psum_bs;
+} cv_spk_conv_params;
+int cv_sizeof_spk_conv_params(void);
+int cv_spk_conv(const cv_spk_conv_params* p, void* stream);
+/* CAM context gate (CAMPPlus.py:95-112) from the 4-row sums psum [B][groups][128] of the bottleneck activation:
+ * gate[b][s][32] = sigmoid(w2 [32][64] relu(w1 [64][128] (mean_{t<len} + mean_{segment s, t<len}) + b1) + b2), segments of
+ * seg_len frames (seg_len % 4 == 0), ceil(T / seg_len) of them. */
+int cv_spk_cam_gate(const float* psum, int64_t psum_bs, const int32_t* len, int32_t B, int32_t T, int32_t seg_len, const float* w1,
+                    const float* b1, const float* w2, const float* b2, float* gate, int64_t gate_bs, void* stream);
+/* out[b] = [mean | unbiased std] over t < len[b] of relu(x * pre_scale + pre_shift) (BN -> ReLU, or x itself when pre_scale is
+ * NULL), C channels (C % 64 == 0), len[b] >= 2 (CAMPPlus.py:35-46) */
+int cv_spk_stats_pool(const float* x, int64_t x_bs, int32_t ldx, const int32_t* len, int32_t B, int32_t T, int32_t C,
+                      const float* pre_scale, const float* pre_shift, float* out, int64_t out_bs, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * hipGraph capture of a launch sequence issued through this ABI on `stream` (the reference's counterpart is
  * torch.cuda.CUDAGraph capture in llm/qwen2_5.py:97-124).  begin/end bracket the launches; launch replays them.
  * ------------------------------------------------------------------------------------------ */
