@@ -23,14 +23,26 @@ __global__ __launch_bounds__(256) void norm_kernel(const cv_norm_params p) {
     v[i] = make_float4(t.x * mk, t.y * mk, t.z * mk, t.w * mk);
     s += v[i].x + v[i].y + v[i].z + v[i].w;
   }
-  float mean = 0.f;
-  if (!p.rms) mean = wave_sum(s) / (float)p.dim;
+  // The mean is carried as mean + mean_lo: one fp32 cannot hold the mean of a row with a large common offset (x = 1000 + N(0, 1): half an
+  // ulp of 1000 is 3e-5 of the spread, and the rounding of the 1e6-sized sum is larger still), so the residual of the first estimate is
+  // summed from the registers — x - mean is exact there — and subtracted as well.
+  float mean = 0.f, mean_lo = 0.f;
+  if (!p.rms) {
+    mean = wave_sum(s) / (float)p.dim;
+    float r = 0.f;
+#pragma unroll
+    for (int i = 0; i < MAXV; ++i) {
+      const int c = i * 64 + lane;
+      if (c < nv) r += ((v[i].x - mean) + (v[i].y - mean)) + ((v[i].z - mean) + (v[i].w - mean));
+    }
+    mean_lo = wave_sum(r) / (float)p.dim;
+  }
   float q = 0.f;
 #pragma unroll
   for (int i = 0; i < MAXV; ++i) {
     const int c = i * 64 + lane;
     if (c < nv) {
-      const float a = v[i].x - mean, b = v[i].y - mean, cc = v[i].z - mean, d = v[i].w - mean;
+      const float a = (v[i].x - mean) - mean_lo, b = (v[i].y - mean) - mean_lo, cc = (v[i].z - mean) - mean_lo, d = (v[i].w - mean) - mean_lo;
       q += a * a + b * b + cc * cc + d * d;
     }
   }
@@ -52,7 +64,7 @@ __global__ __launch_bounds__(256) void norm_kernel(const cv_norm_params p) {
     const float gg[4] = {g4.x, g4.y, g4.z, g4.w}, bb[4] = {b4.x, b4.y, b4.z, b4.w}, aa[4] = {a4.x, a4.y, a4.z, a4.w};
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      float y = (o[r] - mean) * rstd * gg[r] + bb[r];
+      float y = ((o[r] - mean) - mean_lo) * rstd * gg[r] + bb[r];
       if (p.act == CV_ACT_MISH) y = act_mish(y);
       else if (p.act == CV_ACT_LEAKY) y = fmaxf(y, 0.f);   // ReLU (the params carry no slope): LegacyLinearNoSubsampling
       y += aa[r];

@@ -69,3 +69,70 @@ def test_argument_validation_returns_status_codes_without_a_gpu():
     assert lib.cv_snake_multi(one, 4, 16, 16, 1, ptrs, ptrs, 12, L.CV_F32X3, null) < 0
     assert lib.cv_tblock_head(None, null) < 0 and lib.cv_tblock_tail(None, null) < 0
     assert lib.cv_hift_decode_enqueue(None, null) < 0
+
+
+def test_version_and_unbound_entry_points_reject_null_arguments():
+    """cv_version, and the entry points no Python wrapper calls (aliases of cv_graph_launch / cv_graph_destroy / cv_hift_decode_enqueue, and
+    the *_enqueue forms of the composed stages): they answer, and reject null descriptors / handles with a status code."""
+    from cosyvoice_amd import _lib as L
+    lib = L.lib()
+    null = ctypes.c_void_p(None)
+    assert lib.cv_version() >= 1
+    assert lib.cv_llm_step_enqueue(None, null) < 0 and lib.cv_flow_euler_enqueue(None, null) < 0 and lib.cv_hift_decode(None, null) < 0
+    assert lib.cv_llm_step_graph_launch(null, null) < 0 and lib.cv_llm_step_graph_destroy(null) < 0
+    assert lib.cv_flow_euler_graph_launch(null, null) < 0 and lib.cv_flow_euler_graph_destroy(null) < 0
+    assert lib.cv_hift_decode_graph_create(None, null, None) < 0 and lib.cv_graph_end(null, None) < 0
+
+
+# Where every entry point of the C ABI is exercised WITH DATA: export -> test module, or (test module, the token in that module that reaches
+# it when neither the export's name nor ``ops.<name without cv_>`` appears there).  "lifecycle": create / destroy / sizeof entries, run by
+# every test that loads the library or builds a model.  "test_abi_cpu": answered / rejected with null arguments only — these have no data
+# test of their own (aliases of tested entry points, and the eager *_enqueue forms of stages that the tests run through *_graph_create).
+# A new export fails test_every_export_has_a_test_module until somebody decides where it is tested.
+_HELPERS, _GRAPH = "test_helper_kernels_gpu", ("test_flow_gpu", "use_graph = True")
+COVERAGE = {
+    "cv_version": "test_abi_cpu", "cv_arch": "test_abi_cpu",
+    "cv_gemm": "test_gemm_modes_gpu", "cv_layernorm": "test_gemm_gpu", "cv_attention": "test_attention_gpu",
+    "cv_sizeof_gemm_params": "lifecycle", "cv_sizeof_norm_params": "lifecycle", "cv_sizeof_attn_params": "lifecycle",
+    "cv_to_channels_last": _HELPERS, "cv_to_channels_first": _HELPERS, "cv_snake_multi": _HELPERS, "cv_stft16": _HELPERS,
+    "cv_istft16": _HELPERS, "cv_hift_source": _HELPERS, "cv_embedding": _HELPERS, "cv_est_pack": _HELPERS, "cv_cfm_update": _HELPERS,
+    "cv_graph_begin": _GRAPH, "cv_graph_end": _GRAPH, "cv_graph_launch": _GRAPH, "cv_graph_destroy": "lifecycle",
+    "cv_graph_launch_direct": ("test_model_gpu", "cu_partition"), "cv_graph_num_launches": ("test_speaker_gpu", "num_launches"),
+    "cv_stream_create_cumask": ("test_model_gpu", "cu_partition"), "cv_stream_destroy": "lifecycle",
+    "cv_skinny_gemm": "test_llm_gpu", "cv_pack_skinny": "test_llm_gpu", "cv_rmsnorm_reduce": "test_llm_gpu", "cv_rope_append": "test_llm_gpu",
+    "cv_decode_attention": "test_llm_gpu", "cv_kv_retile": "test_llm_gpu", "cv_sample_ras": "test_llm_gpu",
+    "cv_sizeof_skinny_params": "lifecycle", "cv_sizeof_sample_params": "lifecycle",
+    "cv_anti_alias_act": "test_bigvgan_gpu", "cv_anti_alias_act_cl": "test_bigvgan_gpu",
+    "cv_stft_magnitude": _HELPERS, "cv_log_clamp_channels_first": _HELPERS,
+    "cv_groupnorm_cl": "test_flow_v1_gpu", "cv_groupnorm_workspace_floats": ("test_flow_v1_gpu", "ops.groupnorm_workspace"),
+    "cv_interp_linear_cl": _HELPERS, "cv_sizeof_groupnorm_params": "lifecycle", "cv_relpos_append": _HELPERS,
+    "cv_sizeof_tblock_params": "lifecycle", "cv_tblock_head": "test_tblock_gpu", "cv_tblock_tail": "test_tblock_gpu",
+    "cv_tblock_tail_head": "test_tblock_gpu",
+    "cv_sizeof_llm_step_desc": "lifecycle", "cv_sizeof_llm_layer": "lifecycle", "cv_llm_step_enqueue": "test_abi_cpu",
+    "cv_llm_step_graph_create": "test_llm_gpu", "cv_llm_step_graph_launch": "test_abi_cpu", "cv_llm_step_graph_destroy": "lifecycle",
+    "cv_sizeof_resblock_params": "lifecycle", "cv_resblock_conv1": "test_tblock_gpu", "cv_resblock_conv2": "test_tblock_gpu",
+    "cv_sizeof_flow_solver_desc": "lifecycle", "cv_sizeof_flow_block": "lifecycle", "cv_sizeof_flow_tblock": "lifecycle",
+    "cv_flow_euler_enqueue": "test_abi_cpu", "cv_flow_euler_graph_create": "test_tblock_gpu", "cv_flow_euler_graph_launch": "test_abi_cpu",
+    "cv_flow_euler_graph_destroy": "lifecycle",
+    "cv_sizeof_hift_decode_desc": "lifecycle", "cv_sizeof_hift_stage": "lifecycle", "cv_sizeof_hift_resunit": "lifecycle",
+    "cv_hift_decode_enqueue": "test_hift_gpu", "cv_hift_decode": "test_abi_cpu", "cv_hift_decode_graph_create": "lifecycle",
+    "cv_spk_power": ("test_speaker_gpu", "test_fbank_matches_restatement"), "cv_spk_log_cmn": ("test_speaker_gpu", "test_fbank_matches_restatement"),
+    "cv_sizeof_spk_conv_params": "lifecycle",
+    "cv_spk_conv": "test_speaker_gpu", "cv_spk_cam_gate": "test_speaker_gpu", "cv_spk_stats_pool": "test_speaker_gpu",
+}
+
+
+def test_every_export_has_a_test_module():
+    from cosyvoice_amd import _lib
+    assert set(COVERAGE) == set(_lib.EXPORTS), (sorted(set(_lib.EXPORTS) - set(COVERAGE)), sorted(set(COVERAGE) - set(_lib.EXPORTS)))
+    here = os.path.dirname(os.path.abspath(__file__))
+    for name, where in COVERAGE.items():
+        if where == "lifecycle":
+            assert re.search(r"sizeof|create|destroy", name), f"{name} is not a create / destroy / sizeof entry"
+            continue
+        module, token = where if isinstance(where, tuple) else (where, None)
+        path = os.path.join(here, module + ".py")
+        assert os.path.exists(path), f"{name}: {module}.py does not exist"
+        text = open(path).read()
+        pat = re.escape(token) if token else rf"\b{name}\b|\bops\.{name[3:]}\b"
+        assert re.search(pat, text), f"{name}: tests/{module}.py names neither it nor its ops wrapper"

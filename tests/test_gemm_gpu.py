@@ -1,7 +1,14 @@
 """GPU: cv_gemm / cv_layernorm through the C ABI against plain torch fp32 references of the same op."""
+import os
+import sys
+
 import pytest
 import torch
 import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _helpers as H  # noqa: E402
+from _helpers import unsplit as _unsplit  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -104,6 +111,33 @@ def test_layernorm(odt, rows, dim, rms):
     assert _rel(oa, ref) < {torch.float32: 1e-6, torch.bfloat16: 5e-3, torch.float16: 6e-4}[odt]
 
 
+@pytest.mark.parametrize("odt", DTS)
+@pytest.mark.parametrize("act", ["NONE", "MISH"])
+@pytest.mark.parametrize("rpg", [1, 37])
+@pytest.mark.parametrize("dim", [80, 256, 1024])
+def test_layernorm_modes(dim, rpg, act, odt):
+    """add with rows_per_group 1 and T, act = MISH, out_scale != 1, ldx / add_ld / ldo > dim, rows with a large common offset
+    (x = 1000 + N(0, 1)), against F.layer_norm in float64; test_layernorm's bounds.  The kernel adds the group vector AFTER the activation
+    (CausalBlock1D's Mish, then the time embedding).  Outputs are pre-filled with NaN; the input's padding columns hold NaN."""
+    from cosyvoice_amd import ops
+    scale = 0.5
+    x, g, b, add, ref = H.layernorm_case(dim, rpg, act, scale, torch.float64)
+    rows = x.shape[0]
+    xin, addin = H.nan_like((rows + 2, dim + 8), torch.float32), H.nan_like((add.shape[0], dim + 12), torch.float32)
+    xin[:rows, :dim], addin[:, :dim] = x.cuda(), add.cuda()
+    o32, oa = H.nan_like((rows + 2, dim + 4), torch.float32), H.nan_like((rows + 2, dim + 8), odt)
+    ops.layernorm(xin[:rows, :dim], g.cuda(), b.cuda(), 1e-5, add=addin[:, :dim], rows_per_group=rpg, act=getattr(ops, "ACT_" + act),
+                  out_scale=scale, out_f32=o32[:rows, :dim], out_act=oa[:rows, :dim])
+    torch.cuda.synchronize()
+    o32, oa = o32.cpu(), oa.cpu()
+    for o in (o32, oa):
+        assert bool(torch.isnan(o[rows:].float()).all()) and bool(torch.isnan(o[:, dim:].float()).all()), "layernorm wrote outside (rows, dim)"
+    err = (o32[:rows, :dim].double() - ref).abs().max().item()
+    assert err < 2e-5 * ref.abs().max().item() + 1e-5, f"max|err| {err:.3e}, max|ref| {ref.abs().max().item():.3e}"
+    rel = ((oa[:rows, :dim].double() - ref).norm() / ref.norm()).item()
+    assert rel < {torch.float32: 1e-6, torch.bfloat16: 5e-3, torch.float16: 6e-4}[odt], f"relative L2 {rel:.3e}"
+
+
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
 def test_tall_gemm_tile_plain_and_swiglu(dt):
     """>= 8192 rows with N, K >= 512 take the 8-wave 128 x 128 tile (the LLM prefill of a 4-batch decode job): plain epilogue with a
@@ -124,13 +158,6 @@ def test_tall_gemm_tile_plain_and_swiglu(dt):
     torch.cuda.synchronize()
     assert _rel(o32, x.float() @ W.float().t() + res) < TOL[dt] * 0.5
     assert _rel(h, F.silu(x.float() @ g.float().t()) * (x.float() @ u.float().t())) < TOL[dt]
-
-
-def _unsplit(t):
-    """pre-split fp32-sized storage (.., C) -> the fp32 values hi + lo it stands for."""
-    raw = t.contiguous().view(torch.int16).reshape(*t.shape[:-1], t.shape[-1] // 8, 16)
-    hi, lo = raw[..., :8].contiguous().view(torch.bfloat16), raw[..., 8:].contiguous().view(torch.bfloat16)
-    return (hi.float() + lo.float()).reshape(t.shape)
 
 
 @pytest.mark.parametrize("shape", ["auto", "4x1", "2x2", "2x1", "1x2", "1x1"])
