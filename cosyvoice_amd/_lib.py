@@ -37,6 +37,7 @@ class GemmParams(C.Structure):
         ("k_out", _vp), ("k_bs", _i64), ("ldk", _i32),
         ("vt_out", _vp), ("vt_heads", _i32), ("vt_ld", _i32),
         ("x3_flags", _i32), ("reserved_x3", _i32),
+        ("len_base", _vp), ("a_len_mul", _i32), ("a_len_add", _i32), ("m_len_mul", _i32), ("m_len_add", _i32),
     ]
 
 
@@ -234,7 +235,7 @@ class HiftDecodeDesc(C.Structure):
     _fields_ = [("dtype", _i32), ("gemm_dtype", _i32), ("B", _i32), ("T", _i32), ("S", _i32), ("n_stages", _i32), ("n_kernels", _i32),
                 ("stft_ld", _i32), ("hop", _i32), ("presplit", _i32), ("lrelu_slope", _f32), ("audio_limit", _f32),
                 ("conv_pre", HiftConv), ("conv_post", HiftConv), ("stages", C.POINTER(HiftStage)),
-                ("mel_cl", _vp), ("s", _vp), ("stft", _vp), ("a_pre", _vp), ("post", _vp), ("wav", _vp)]
+                ("mel_cl", _vp), ("s", _vp), ("stft", _vp), ("a_pre", _vp), ("post", _vp), ("wav", _vp), ("lens", _vp)]
 
 
 _lib = None

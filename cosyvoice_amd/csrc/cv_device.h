@@ -133,3 +133,10 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+
+// Internal launchers shared between translation units (not part of the C ABI): the length-aware source STFT / iSTFT of a ragged
+// HiFT decode (hift.hip; cv_hift_decode_desc.lens).  lens = DEVICE int32 [B] frames per utterance, T = padded frame count.
+__attribute__((visibility("hidden"))) int hift_stft16_ragged(const float* s, void* out, int32_t dtype, int32_t B, int32_t S, int32_t ldo,
+                                                             const int32_t* lens, int32_t T, void* stream);
+__attribute__((visibility("hidden"))) int hift_istft16_ragged(const float* y, float* wav, int32_t B, int32_t F, int32_t ldy, float audio_limit,
+                                                              const int32_t* lens, int32_t T, void* stream);

@@ -269,6 +269,16 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_kernel(const cv_gemm_params
   const int z = blockIdx.z;
   const int z1 = z / p.batch_inner, z0 = z - z1 * p.batch_inner;
 
+  // ragged batches (cv_gemm_params.len_base): this batch index's own A extent and needed output rows — one scalar load per workgroup,
+  // workgroup-uniform, before the first LDS use.  A tile that lies wholly past the needed rows costs nothing; addresses stay clamped
+  // with p.a_rows (the buffer's extent), the device value only decides what reads as zero.
+  int a_len = p.a_rows;
+  if (p.len_base) {
+    const int base = __builtin_amdgcn_readfirstlane(p.len_base[z]);
+    if ((p.m_len_mul | p.m_len_add) && m0 >= base * p.m_len_mul + p.m_len_add) return;
+    if (p.a_len_mul | p.a_len_add) a_len = min(a_len, base * p.a_len_mul + p.a_len_add);
+  }
+
   const char* Ab = (const char*)p.A + (z0 * p.a_bs0 + z1 * p.a_bs1) * ES;
   const char* Wb = (const char*)p.W + (z0 * p.w_bs0 + z1 * p.w_bs1) * ES;
 
@@ -298,7 +308,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_kernel(const cv_gemm_params
     const int arow = a_rowbase[i];
     const int arc = min(max(arow, 0), p.a_rows - 1);
     a_ptr[i] = Ab + ((int64_t)arc * p.lda + k) * ES;
-    if (!conv) a_m_ok[i] = a_m_ok[i] && (arow >= 0) && (arow < p.a_rows);
+    if (!conv) a_m_ok[i] = a_m_ok[i] && (arow >= 0) && (arow < a_len);
   }
   int b_ok[B_CH], b_lds[B_CH], b_lds2[B_CH], b_k[B_CH];
   const char* b_ptr[B_CH];
@@ -334,7 +344,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_kernel(const cv_gemm_params
       for (int i = 0; i < A_CH; ++i) {
         const int k = kbase + ((i * NTHR + tid) & 7) * CH;
         const int arow = a_rowbase[i] + a_tap[i] * p.tap_step;
-        const bool ok = a_m_ok[i] && (k < p.K) && (arow >= 0) && (arow < p.a_rows);
+        const bool ok = a_m_ok[i] && (k < p.K) && (arow >= 0) && (arow < a_len);
         const int arc = min(max(arow, 0), p.a_rows - 1);
         const int tapc = k < p.K ? a_ci[i] : 0;
         ra[i] = *(const uint4*)(Ab + ((int64_t)arc * p.lda + tapc) * ES);
@@ -502,6 +512,12 @@ __global__ __launch_bounds__(256) void gemm_ring_kernel(const cv_gemm_params p) 
   const int m0 = tile_m * BM, n0 = tile_n * BN;
   const int z = blockIdx.z;
   const int z1 = z / p.batch_inner, z0 = z - z1 * p.batch_inner;
+  int a_len = p.a_rows;   // ragged batches: as in gemm_kernel
+  if (p.len_base) {
+    const int base = __builtin_amdgcn_readfirstlane(p.len_base[z]);
+    if ((p.m_len_mul | p.m_len_add) && m0 >= base * p.m_len_mul + p.m_len_add) return;
+    if (p.a_len_mul | p.a_len_add) a_len = min(a_len, base * p.a_len_mul + p.a_len_add);
+  }
   const char* Ab = (const char*)p.A + (z0 * p.a_bs0 + z1 * p.a_bs1) * ES;
   const char* Wb = (const char*)p.W + (z0 * p.w_bs0 + z1 * p.w_bs1) * ES;
   const int nk = (p.K + BK - 1) / BK;
@@ -527,7 +543,7 @@ __global__ __launch_bounds__(256) void gemm_ring_kernel(const cv_gemm_params p) 
       rowbase[j] = m * p.a_row_stride + p.tap_base;
       rok[j] = m < p.M;
       const int arow = rowbase[j];
-      if (!conv) rok[j] = rok[j] && arow >= 0 && arow < p.a_rows;
+      if (!conv) rok[j] = rok[j] && arow >= 0 && arow < a_len;
       rptr[j] = Ab + ((int64_t)min(max(arow, 0), p.a_rows - 1) * p.lda + kch[j] * CH) * ES;
     } else {
       const int n = n0 + row;
@@ -547,7 +563,7 @@ __global__ __launch_bounds__(256) void gemm_ring_kernel(const cv_gemm_params p) 
       if (load_a && conv) {
         const int tap = k / p.cin, ci = k - tap * p.cin;
         const int arow = rowbase[j] + tap * p.tap_step;
-        const bool ok = rok[j] && k < p.K && arow >= 0 && arow < p.a_rows;
+        const bool ok = rok[j] && k < p.K && arow >= 0 && arow < a_len;
         src = ok ? Ab + ((int64_t)arow * p.lda + ci) * ES : zero;
       } else {
         const bool ok = rok[j] && k < p.K;
@@ -758,6 +774,7 @@ constexpr int CONV_WIN_NO = 1;
 int dispatch_conv_win(const cv_gemm_params& p, hipStream_t st) {
   int force_wm = 0, force_wn = 0;
   if (const char* e = getenv("CV_CONV_WIN"); !e || atoi(e) != 1) return CONV_WIN_NO;
+  if (p.len_base) return CONV_WIN_NO;   // ragged batches: the window loader knows one a_rows for the whole launch
   if (const char* s = getenv("CV_CONV_WIN_SHAPE"); s && s[0] >= '1' && s[0] <= '4' && s[1] == 'x' && s[2] >= '1' && s[2] <= '2') { force_wm = s[0] - '0'; force_wn = s[2] - '0'; }
   if (p.cin == p.K || (p.x3_flags & 3) != 3 || p.a_row_stride != 1 || p.tap_step <= 0) return CONV_WIN_NO;
   if ((p.cin & 63) || (p.N & 63) || p.act == CV_ACT_SWIGLU || p.out_mode != CV_OUT_ROWMAJOR) return CONV_WIN_NO;
@@ -866,6 +883,13 @@ extern "C" int cv_gemm(const cv_gemm_params* pp, void* stream) {
   if (p.x3_flags && (!x3 || (p.x3_flags & ~7))) return CV_ERR_ARG;          // pre-split storage belongs to CV_F32X3 launches
   if ((p.x3_flags & 4) && (!p.out_act || (p.N & 7) || (p.ldoa & 7) || p.act == CV_ACT_SWIGLU || p.out_mode != CV_OUT_ROWMAJOR)) return CV_ERR_ARG;
   if ((p.x3_flags & 3) && ((p.K & 7) || (p.cin & 7) || (p.lda & 7) || (p.ldw & 7))) return CV_ERR_ARG;   // 8-value groups
+  if (!p.len_base) {   // ragged-batch fields without the length array
+    if (p.a_len_mul | p.a_len_add | p.m_len_mul | p.m_len_add) return CV_ERR_ARG;
+  } else {
+    if (((uintptr_t)p.len_base & 3) || p.a_len_mul < 0 || p.m_len_mul < 0) return CV_ERR_ARG;
+    if (!(p.a_len_mul | p.a_len_add) && !(p.m_len_mul | p.m_len_add)) return CV_ERR_ARG;   // lengths that bound nothing
+    if (p.batch_inner != p.batch || p.out_mode != CV_OUT_ROWMAJOR) return CV_ERR_UNSUPPORTED;   // one length per grid.z index
+  }
   hipStream_t st = (hipStream_t)stream;
   if (x3) return dispatch_x3(p, st);
   switch (p.dtype) {

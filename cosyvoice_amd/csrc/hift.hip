@@ -87,14 +87,21 @@ __constant__ float c_cos16[16] = {1.f, 0.92387953251f, 0.70710678118f, 0.3826834
 __device__ __forceinline__ float hann16(int n) { return 0.5f - 0.5f * c_cos16[n & 15]; }
 
 // ---- STFT: one thread per (frame, bin k in 0..8) computes real+imag
+// Ragged batches (lens != NULL, cv_hift_decode_desc.lens): row b holds S_b = lens[b] * len_mul <= S samples; the reflect padding turns at
+// S_b and frames past S_b / 4 are not written (nothing reads them: the consuming conv is bounded by the same length).  The row pitch stays S / F.
 template <int DT>
-__global__ __launch_bounds__(256) void stft16_kernel(const float* s, void* out, int S, int F, int ldo) {
+__global__ __launch_bounds__(256) void stft16_kernel(const float* s, void* out, int S, int F, int ldo, const int32_t* lens, int len_mul,
+                                                     int len_max) {
   const int b = blockIdx.y;
   const int idx = blockIdx.x * 256 + threadIdx.x;
   const int f = idx / 12, k = idx - f * 12;  // 12 lanes per frame: 9 bins + 3 lanes for zero padding columns
-  if (f >= F) return;
-  const float* x = s + (int64_t)b * S;
   const int64_t ob = ((int64_t)b * F + f) * ldo;
+  const float* x = s + (int64_t)b * S;
+  if (lens) {   // the device value is clamped to [1, len_max]: it never moves an address out of the row
+    S = min(max(lens[b], 1), len_max) * len_mul;
+    F = S / 4 + 1;
+  }
+  if (f >= F) return;
   if (k >= 9) {
     for (int c = 18 + (k - 9); c < ldo; c += 3) st<DT>(out, ob + c, 0.f);
     return;
@@ -115,10 +122,19 @@ __global__ __launch_bounds__(256) void stft16_kernel(const float* s, void* out, 
 }
 
 // ---- iSTFT: block = 64 frames -> 256 output samples; frames (+3 halo before) staged in LDS as real/imag
-__global__ __launch_bounds__(256) void istft16_kernel(const float* y, float* wav, int F, int ldy, float limit) {
+// Ragged batches (lens != NULL): row b has F_b = lens[b] * len_mul + 1 <= F frames; the overlap-add, its envelope and the output end at F_b
+// (frames past it hold padding), blocks past it return before touching LDS.  The row pitch stays F / (F - 1) * 4.
+__global__ __launch_bounds__(256) void istft16_kernel(const float* y, float* wav, int F, int ldy, float limit, const int32_t* lens,
+                                                      int len_mul, int len_max) {
   __shared__ float sre[67][9], sim[67][9];
   const int b = blockIdx.y;
   const int f0 = blockIdx.x * 64;           // outputs n' in [4 f0, 4 f0 + 256)
+  y += (int64_t)b * F * ldy;
+  wav += (int64_t)b * (F - 1) * 4;
+  if (lens) {
+    F = min(max(lens[b], 1), len_max) * len_mul + 1;
+    if (f0 >= F - 1) return;
+  }
   const int L = (F - 1) * 4;
   // frames covering sample n = n' + 8: f in [ceil((n-15)/4), floor(n/4)] -> for the block: f0 - 1 .. f0 + 65
   for (int i = threadIdx.x; i < 67 * 9; i += 256) {
@@ -126,7 +142,7 @@ __global__ __launch_bounds__(256) void istft16_kernel(const float* y, float* wav
     const int f = f0 - 1 + fl;
     float re = 0.f, im = 0.f;
     if (f >= 0 && f < F) {
-      const float* row = y + ((int64_t)b * F + f) * ldy;
+      const float* row = y + (int64_t)f * ldy;
       const float mag = fminf(__expf(row[k]), 100.0f);
       const float ph = sinf(row[9 + k]);
       float sn, cs;
@@ -161,7 +177,7 @@ __global__ __launch_bounds__(256) void istft16_kernel(const float* y, float* wav
   }
   float o = acc / env;
   o = fminf(fmaxf(o, -limit), limit);
-  wav[(int64_t)b * L + np] = o;
+  wav[np] = o;
 }
 
 // ---- source: (1) frame-start phases per (b, harmonic) in fp64, (2) per-sample synthesis + tanh(linear)
@@ -249,7 +265,25 @@ extern "C" int cv_stft16(const float* s, void* out, int32_t dtype, int32_t B, in
   if (!s || !out || B <= 0 || S < 16 || (S & 3) || ldo < 18) return CV_ERR_ARG;
   const int F = S / 4 + 1;
   dim3 grid((F * 12 + 255) / 256, B);
-  DISPATCH_DT(dtype, hipLaunchKernelGGL(stft16_kernel<DT>, grid, dim3(256), 0, (hipStream_t)stream, s, out, S, F, ldo));
+  DISPATCH_DT(dtype, hipLaunchKernelGGL(stft16_kernel<DT>, grid, dim3(256), 0, (hipStream_t)stream, s, out, S, F, ldo, (const int32_t*)nullptr, 0, 0));
+  CV_CHECK_LAUNCH();
+  return CV_OK;
+}
+
+// internal (cv_device.h): the ragged forms used by cv_hift_decode_enqueue; lens = DEVICE int32 [B] frames per row, T = the padded frame count
+int hift_stft16_ragged(const float* s, void* out, int32_t dtype, int32_t B, int32_t S, int32_t ldo, const int32_t* lens, int32_t T, void* stream) {
+  if (!s || !out || !lens || B <= 0 || T <= 0 || S < 16 || (S % T) || ((S / T) & 3) || S / T < 16 || ldo < 18) return CV_ERR_ARG;
+  const int F = S / 4 + 1;
+  dim3 grid((F * 12 + 255) / 256, B);
+  DISPATCH_DT(dtype, hipLaunchKernelGGL(stft16_kernel<DT>, grid, dim3(256), 0, (hipStream_t)stream, s, out, S, F, ldo, lens, S / T, T));
+  CV_CHECK_LAUNCH();
+  return CV_OK;
+}
+
+int hift_istft16_ragged(const float* y, float* wav, int32_t B, int32_t F, int32_t ldy, float audio_limit, const int32_t* lens, int32_t T, void* stream) {
+  if (!y || !wav || !lens || B <= 0 || T <= 0 || F < 2 || ((F - 1) % T) || ldy < 18) return CV_ERR_ARG;
+  dim3 grid((F - 1 + 63) / 64, B);
+  hipLaunchKernelGGL(istft16_kernel, grid, dim3(256), 0, (hipStream_t)stream, y, wav, F, ldy, audio_limit, lens, (F - 1) / T, T);
   CV_CHECK_LAUNCH();
   return CV_OK;
 }
@@ -257,7 +291,7 @@ extern "C" int cv_stft16(const float* s, void* out, int32_t dtype, int32_t B, in
 extern "C" int cv_istft16(const float* y, float* wav, int32_t B, int32_t F, int32_t ldy, float audio_limit, void* stream) {
   if (!y || !wav || B <= 0 || F < 2 || ldy < 18) return CV_ERR_ARG;
   dim3 grid((F - 1 + 63) / 64, B);
-  hipLaunchKernelGGL(istft16_kernel, grid, dim3(256), 0, (hipStream_t)stream, y, wav, F, ldy, audio_limit);
+  hipLaunchKernelGGL(istft16_kernel, grid, dim3(256), 0, (hipStream_t)stream, y, wav, F, ldy, audio_limit, (const int32_t*)nullptr, 0, 0);
   CV_CHECK_LAUNCH();
   return CV_OK;
 }

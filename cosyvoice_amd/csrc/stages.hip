@@ -266,13 +266,18 @@ extern "C" int cv_flow_euler_graph_destroy(void* graph) { return cv_graph_destro
 // cv_hift_decode_*: HiFTGenerator.decode, hifigan/generator.py:349-381 (ResBlock :91-98, SourceModule STFT :333-347).  The launch
 // sequence is the one cosyvoice_amd/hift.py composes (_decode_cl_impl / _resblock) and is tested equal to it.
 namespace {
+// Ragged batches (cv_hift_decode_desc.lens): utterance b has T_b = lens[b] frames; a tensor with `mul` rows per frame (+ `add`) has
+// T_b * mul + add valid rows.  Len{0, 0} = the whole padded extent.
+struct Len { int mul = 0, add = 0; };
+
 struct Epi {   // epilogue of one conv launch
   const float* res = nullptr; const float* res2 = nullptr; float out_scale = 1.0f;
   int act = CV_ACT_NONE; const float* act_param = nullptr; float act_slope = 0.0f;
   float* out_f32 = nullptr; int ldo32 = 0; void* out_act = nullptr;
 };
 
-int hconv(const cv_hift_decode_desc& d, const cv_hift_conv& c, const void* x, int T_in, int T_out, const Epi& e, hipStream_t st) {
+int hconv(const cv_hift_decode_desc& d, const cv_hift_conv& c, const void* x, int T_in, int T_out, const Epi& e, hipStream_t st,
+          Len in = Len{}, Len out = Len{}) {
   cv_gemm_params p{};
   p.dtype = d.gemm_dtype; p.M = T_out; p.N = c.cout; p.K = c.k * c.cin; p.batch = d.B;
   p.A = x; p.a_bs0 = (int64_t)T_in * c.cin; p.lda = c.cin; p.a_rows = T_in;
@@ -285,27 +290,28 @@ int hconv(const cv_hift_decode_desc& d, const cv_hift_conv& c, const void* x, in
   if (e.out_act) { p.out_act = e.out_act; p.oa_bs0 = (int64_t)T_out * c.cout; p.ldoa = c.cout; }
   p.out_row_stride = 1;
   p.x3_flags = e.out_act ? c.x3_flags : (c.x3_flags & ~4);
+  if (d.lens) { p.len_base = d.lens; p.a_len_mul = in.mul; p.a_len_add = in.add; p.m_len_mul = out.mul; p.m_len_add = out.add; }
   return cv_gemm(&p, st);
 }
 
 // ResBlock (generator.py:91-98): x -> x + c2(snake(c1(snake(x)))) per unit; xa = snake_{a1[0]}(x32) already computed
 int hresblock(const cv_hift_decode_desc& d, const cv_hift_resblock& rb, const cv_hift_stage& sg, const float* x32, const void* xa,
-              const Epi& fin, hipStream_t st) {
+              const Epi& fin, hipStream_t st, Len len) {
   const float* cur32 = x32;
   const void* cur_a = xa;
   const int t = sg.t_out;
   for (int j = 0; j < rb.n_units; ++j) {
     const cv_hift_resunit& u = rb.units[j];
     Epi e1; e1.act = CV_ACT_SNAKE; e1.act_param = u.a2; e1.out_act = sg.ta;
-    if (int rc = hconv(d, u.c1, cur_a, t, t, e1, st)) return rc;
+    if (int rc = hconv(d, u.c1, cur_a, t, t, e1, st, len, len)) return rc;
     if (j < rb.n_units - 1) {
       float* nxt = (j & 1) ? sg.r1 : sg.r0;
       Epi e2; e2.res = cur32; e2.out_f32 = nxt; e2.act = CV_ACT_SNAKE; e2.act_param = rb.units[j + 1].a1; e2.out_act = sg.ra;
-      if (int rc = hconv(d, u.c2, sg.ta, t, t, e2, st)) return rc;
+      if (int rc = hconv(d, u.c2, sg.ta, t, t, e2, st, len, len)) return rc;
       cur32 = nxt; cur_a = sg.ra;
     } else {
       Epi e2 = fin; e2.res = cur32;
-      if (int rc = hconv(d, u.c2, sg.ta, t, t, e2, st)) return rc;
+      if (int rc = hconv(d, u.c2, sg.ta, t, t, e2, st, len, len)) return rc;
     }
   }
   return CV_OK;
@@ -313,10 +319,14 @@ int hresblock(const cv_hift_decode_desc& d, const cv_hift_resblock& rb, const cv
 
 int enqueue_hift_decode(const cv_hift_decode_desc& d, hipStream_t st) {
   const int B = d.B, F = d.S / d.hop + 1;
-  if (int rc = cv_stft16(d.s, d.stft, d.dtype, B, d.S, d.stft_ld, st)) return rc;
+  if (d.lens) { if (int rc = hift_stft16_ragged(d.s, d.stft, d.dtype, B, d.S, d.stft_ld, d.lens, d.T, st)) return rc; }
+  else if (int rc = cv_stft16(d.s, d.stft, d.dtype, B, d.S, d.stft_ld, st)) return rc;
+  // rows per mel frame of the tensor at hand (ragged batches): the STFT has F_b = T_b * (S / hop / T) + 1 frames
+  const Len l_stft{d.S / d.hop / d.T, 1};
+  Len l_in{1, 0};
   {
     Epi e; e.act = CV_ACT_LEAKY; e.act_slope = d.lrelu_slope; e.out_act = d.a_pre;
-    if (int rc = hconv(d, d.conv_pre, d.mel_cl, d.T, d.T, e, st)) return rc;
+    if (int rc = hconv(d, d.conv_pre, d.mel_cl, d.T, d.T, e, st, l_in, l_in)) return rc;
   }
   const void* cur_a = d.a_pre;
   int t_in = d.T;
@@ -324,11 +334,12 @@ int enqueue_hift_decode(const cv_hift_decode_desc& d, hipStream_t st) {
     const cv_hift_stage& sg = d.stages[i];
     const int t_out = sg.t_out, c = sg.c;
     const bool last = i == d.n_stages - 1;
+    const Len l_out{l_in.mul * sg.u, last ? 1 : 0};   // the last stage's reflect pad adds its row on the left: + 1 whatever the length
     {   // source branch (generator.py:361-363): strided conv of the source STFT, then its ResBlock -> si1
       Epi e; e.out_f32 = sg.si0; e.act = CV_ACT_SNAKE; e.act_param = sg.source_rb.units[0].a1; e.out_act = sg.xa[0];
-      if (int rc = hconv(d, sg.source_down, d.stft, F, t_out, e, st)) return rc;
+      if (int rc = hconv(d, sg.source_down, d.stft, F, t_out, e, st, l_stft, l_out)) return rc;
       Epi fin; fin.out_f32 = sg.si1;
-      if (int rc = hresblock(d, sg.source_rb, sg, sg.si0, sg.xa[0], fin, st)) return rc;
+      if (int rc = hresblock(d, sg.source_rb, sg, sg.si0, sg.xa[0], fin, st, l_out)) return rc;
     }
     // ups[i] as u phase GEMMs (+ reflect pad on the last stage) + source fusion: x = ups(x) + si (generator.py:355-364)
     auto phase = [&](const cv_hift_phase& ph, int M, int row_off) {
@@ -341,6 +352,8 @@ int enqueue_hift_decode(const cv_hift_decode_desc& d, hipStream_t st) {
       p.out_f32 = sg.x32; p.o32_bs0 = (int64_t)t_out * c; p.ldo32 = c;
       p.out_row_stride = sg.u; p.out_row_off = row_off; p.out_rows = t_out;
       p.x3_flags = sg.up_flags;
+      // ragged: input rows past the utterance's own t_in read as zero; phase rows q >= t_in_b land past its t_out_b (M = 1: the reflect row)
+      if (d.lens) { p.len_base = d.lens; p.a_len_mul = l_in.mul; p.a_len_add = l_in.add; if (M > 1) { p.m_len_mul = l_in.mul; p.m_len_add = l_in.add; } }
       return cv_gemm(&p, st);
     };
     const int off = last ? 1 : 0;
@@ -360,15 +373,17 @@ int enqueue_hift_decode(const cv_hift_decode_desc& d, hipStream_t st) {
       if (j < d.n_kernels - 1) fin.out_f32 = (j & 1) ? sg.acc1 : sg.acc0;
       else { fin.out_scale = 1.0f / d.n_kernels; fin.act = CV_ACT_LEAKY; fin.act_slope = slope; fin.out_act = sg.out; }
       if (j > 0) fin.res2 = ((j - 1) & 1) ? sg.acc1 : sg.acc0;
-      if (int rc = hresblock(d, sg.rbs[j], sg, sg.x32, sg.xa[j], fin, st)) return rc;
+      if (int rc = hresblock(d, sg.rbs[j], sg, sg.x32, sg.xa[j], fin, st, l_out)) return rc;
     }
     cur_a = sg.out;
     t_in = t_out;
+    l_in = l_out;
   }
   {
     Epi e; e.out_f32 = d.post; e.ldo32 = d.stft_ld;
-    if (int rc = hconv(d, d.conv_post, cur_a, t_in, t_in, e, st)) return rc;
+    if (int rc = hconv(d, d.conv_post, cur_a, t_in, t_in, e, st, l_in, l_in)) return rc;
   }
+  if (d.lens) return hift_istft16_ragged(d.post, d.wav, B, t_in, d.stft_ld, d.audio_limit, d.lens, d.T, st);
   return cv_istft16(d.post, d.wav, B, t_in, d.stft_ld, d.audio_limit, st);
 }
 
@@ -387,6 +402,15 @@ int check_hift_desc(const cv_hift_decode_desc* d) {
     if (any_x3 && (g.c & 7)) return CV_ERR_ARG;
   }
   if ((d->presplit || d->conv_pre.x3_flags) && (d->conv_pre.cout & 7)) return CV_ERR_ARG;
+  if (d->lens) {   // ragged batches: every per-stage length is derived from the frame count, so the padded shape has to be the regular one
+    if ((uintptr_t)d->lens & 3) return CV_ERR_ARG;
+    int64_t rows = d->T;
+    for (int i = 0; i < d->n_stages; ++i) {
+      rows *= d->stages[i].u;
+      if (d->stages[i].t_out != rows + (i == d->n_stages - 1 ? 1 : 0)) return CV_ERR_ARG;
+    }
+    if ((int64_t)d->S != rows * d->hop) return CV_ERR_ARG;
+  }
   return CV_OK;
 }
 }  // namespace

@@ -866,10 +866,12 @@ class CausalMaskedDiffWithXvec:
         return bf["mel"][:, :, Tp:2 * Nv]
 
     @torch.no_grad()
-    def inference_ragged(self, tokens, prompt_tokens, prompt_feats, embeddings: torch.Tensor, n_timesteps: int = 10):
+    def inference_ragged(self, tokens, prompt_tokens, prompt_feats, embeddings: torch.Tensor, n_timesteps: int = 10, padded: bool = False):
         """B utterances of DIFFERENT lengths in one batched pass: lists of tokens (Ng_b,), prompt_tokens (Np_b,), prompt_feats
         (2*Np_b, 80); embeddings (B, D).  Returns a list of mels (80, 2*Ng_b) fp32, each identical to its batch-1 result: rows
-        are padded to the longest (rounded up to ``length_bucket``) and the tails masked exactly as in a length-bucketed call."""
+        are padded to the longest (rounded up to ``length_bucket``) and the tails masked exactly as in a length-bucketed call.
+        ``padded``: return instead ONE left-aligned (B, 80, max 2*Ng_b) tensor of its own (the same values; columns past a row's length
+        are unspecified) and the list of lengths 2*Ng_b — what the ragged vocoder takes (HiFTGenerator.inference_ragged)."""
         assert self._loaded
         cfg, dev = self.cfg, self.device
         B = len(tokens)
@@ -901,6 +903,12 @@ class CausalMaskedDiffWithXvec:
         bf["x"].copy_(self.decoder._noise_cl[:T].unsqueeze(0).expand(B, -1, -1))
         self.decoder.solve(bf["x"], ews["mu"], bf["spks"], bf["cond"], n_timesteps, klen=klen_est)
         ops.to_channels_first(bf["x"], bf["mel"])
+        if padded:
+            lens = [2 * (nvs[b] - nps[b]) for b in range(B)]
+            out = torch.empty(B, cfg.output_size, max(lens), device=dev, dtype=torch.float32)
+            for b in range(B):
+                out[b, :, :lens[b]].copy_(bf["mel"][b, :, 2 * nps[b]:2 * nvs[b]])
+            return out, lens
         return [bf["mel"][b, :, 2 * nps[b]:2 * nvs[b]].clone() for b in range(B)]
 
     supports_stream_cache = True

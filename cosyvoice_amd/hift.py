@@ -3,13 +3,14 @@
 (hifigan/f0_predictor.py:19-55).  Same constructor hyper-parameters (via HiftConfig), same
 ``load_state_dict`` key names (legacy weight-norm ``weight_g/weight_v`` folded at load,
 SURVEY.md §8b (i)), same ``inference(speech_feat, cache_source) -> (wav (B,S), source (B,1,S))``
-and ``decode(x, s)`` signatures.  All arithmetic runs in libcosyvoice_amd.so (HIP, gfx950):
+and ``decode(x, s)`` signatures.  Beyond the reference: ``decode_ragged`` / ``inference_ragged`` take B utterances of DIFFERENT
+lengths through one launch sequence and return, per utterance, what the batch-1 call returns.  All arithmetic runs in libcosyvoice_amd.so (HIP, gfx950):
 channels-last activations, every Conv1d / ConvTranspose1d as an implicit-GEMM MFMA launch with
 the Snake / leaky-relu / residual / 1/3-mean fused into the epilogues.
 """
 import math
 import os
-from typing import Dict, Optional
+from typing import Dict, List, Optional, Sequence
 
 import torch
 
@@ -86,6 +87,10 @@ class HiFTGenerator:
         self._loaded = False
         self._ws: Dict[tuple, dict] = {}
         self.use_stage_abi = os.environ.get("CV_HIFT_STAGE_ABI", "1") != "0"   # decode composed by cv_hift_decode_enqueue
+        # ragged calls run at the longest utterance's frame count rounded up to this many frames (100 = 2 s of v2 audio): one workspace and
+        # one descriptor per (B, T) serve every set of lengths <= T, so a service meets a handful of shapes.  The padding costs memory only —
+        # the kernels skip the row tiles past an utterance's own length.
+        self.length_bucket = 100
 
     @property
     def presplit(self):
@@ -224,9 +229,14 @@ class HiFTGenerator:
 
     # ------------------------------------------------------------------ public API
     @torch.no_grad()
-    def f0_predictor(self, speech_feat: torch.Tensor) -> torch.Tensor:
-        """speech_feat (B,80,T) fp32 -> f0 (B,T).  f0_predictor.py:52-55."""
+    def f0_predictor(self, speech_feat: torch.Tensor, lengths: Optional[Sequence[int]] = None) -> torch.Tensor:
+        """speech_feat (B,80,T) fp32 -> f0 (B,T).  f0_predictor.py:52-55.  ``lengths`` (B frame counts <= T): the batch is padded; row b
+        is then, up to its own length, the f0 of that utterance alone (what lies past it is unspecified)."""
         assert self._loaded
+        if lengths is not None:
+            ws, B, T, lens = self._ragged_inputs(speech_feat, lengths)
+            self._f0_from_cl(ws, B, T, lens=ws["lens_dev"])
+            return ws["f0"][:, :max(lens)]
         B, _, T = speech_feat.shape
         ws = self._workspace(B, T)
         x = speech_feat.to(self.device, torch.float32).contiguous()
@@ -234,11 +244,13 @@ class HiFTGenerator:
         self._f0_from_cl(ws, B, T)
         return ws["f0"]
 
-    def _f0_from_cl(self, ws, B, T):
+    def _f0_from_cl(self, ws, B, T, lens=None):
+        """``lens`` (device int32 (B,)): ragged batch — every k=3 conv sees zeros past the utterance's own last frame."""
         cur = ws["mel_cl"]
+        rag = dict(lens=lens, a_len=(1, 0), m_len=(1, 0)) if lens is not None else {}
         for n, c in enumerate(self.f0_convs):
             out = ws["f0_a"][n & 1]
-            self._conv(c, cur, act=ops.ACT_ELU, out_act=out)
+            self._conv(c, cur, act=ops.ACT_ELU, out_act=out, **rag)
             cur = out
         fc = self.cfg.f0_cond_channels
         ops.gemm(cur, self.f0_cls_w, B * T, 4, fc, lda=fc, bias=self.f0_cls_b, out_f32=ws["f0_y"], ldo32=4)
@@ -254,16 +266,21 @@ class HiFTGenerator:
         s2 = s.to(self.device, torch.float32).reshape(B, -1).contiguous()
         return self._decode_cl(ws, B, T, s2)
 
-    def _decode_cl(self, ws, B, T, s2):
+    def _decode_cl(self, ws, B, T, s2, ragged=False):
+        """``ragged``: ws["lens_dev"] holds the frame count of every utterance (cv_hift_decode_desc.lens)."""
+        if ragged and not self.use_stage_abi:
+            raise RuntimeError("the Python-composed decode (use_stage_abi = False) has no ragged form")
         if self.use_stage_abi:
             # stage-level ABI: the library composes the whole decode from a descriptor (cv_hift_decode_enqueue: one foreign call
             # instead of ~100); _decode_cl_impl stays as the cross-check of the C composition (tests/test_hift_gpu.py)
             from . import _lib as L
             import ctypes as C
-            key = ("_desc", self.presplit)
+            key = ("_desc_ragged" if ragged else "_desc", self.presplit)
             ent = ws.get(key)
             if ent is None:
                 ent = ws[key] = self.decode_desc(ws, B, T)
+                if ragged:   # lengths are read on the device: this one descriptor serves every set of lengths <= T
+                    ent[0].lens = ws["lens_dev"].data_ptr()
             desc = ent[0]
             desc.gemm_dtype = L.CV_F32X3 if (self.dtype == torch.float32 and self.f32_products == "bf16x3") else L.TORCH_DT[self.dtype]
             desc.s = s2.data_ptr()
@@ -423,3 +440,95 @@ class HiFTGenerator:
             s[:, :cache_source.shape[2]] = cache_source.to(self.device, torch.float32).reshape(B, -1)
         wav = self._decode_cl(ws, B, T, s)
         return wav, s.unsqueeze(1)
+
+    # ------------------------------------------------------------------ ragged batches (beyond the reference)
+    def _ragged_inputs(self, mels, lengths=None):
+        """mels: list of (80, T_b) / (1, 80, T_b) tensors, or a padded (B, 80, T') tensor with ``lengths``.  Pads to the bucketed T in the
+        (B, T) workspace, writes the device length array (one small copy on the current stream) and the channels-last mel.
+        -> (ws, B, T, lengths as a list)."""
+        assert self._loaded
+        dev = self.device
+        if isinstance(mels, torch.Tensor):
+            assert mels.dim() == 3 and lengths is not None, "a padded (B, 80, T) tensor needs its lengths"
+            lens = [int(v) for v in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
+            B, Tin = mels.shape[0], mels.shape[2]
+            rows = None
+        else:
+            rows = [m.reshape(m.shape[-2], m.shape[-1]) for m in mels]
+            lens = [int(m.shape[1]) for m in rows]
+            assert lengths is None or [int(v) for v in lengths] == lens
+            B, Tin = len(rows), max(lens)
+        if len(lens) != B or min(lens) < 1 or max(lens) > Tin:
+            raise ValueError(f"ragged lengths {lens} do not fit a batch of {B} x {Tin} frames")
+        lb = max(1, int(self.length_bucket or 1))
+        T = -(-max(lens) // lb) * lb
+        ws = self._workspace(B, T)
+        if "lens_dev" not in ws:
+            ws["lens_dev"] = torch.empty(B, device=dev, dtype=torch.int32)
+            ws["mel_in"] = torch.empty(B, self.cfg.in_channels, T, device=dev, dtype=torch.float32)
+        ws["lens_dev"].copy_(torch.tensor(lens, dtype=torch.int32))
+        if rows is None:
+            if Tin == T and mels.is_cuda and mels.dtype == torch.float32 and mels.is_contiguous():
+                src = mels                                  # already in the workspace's shape: no copy
+            else:
+                w = min(Tin, T)
+                ws["mel_in"][:, :, :w].copy_(mels[:, :, :w])
+                src = ws["mel_in"]
+        else:
+            for b, m in enumerate(rows):
+                ws["mel_in"][b, :, :lens[b]].copy_(m)
+            src = ws["mel_in"]
+        ops.to_channels_last(src, ws["mel_cl"])
+        return ws, B, T, lens
+
+    @staticmethod
+    def _ragged_rows(x, B, what):
+        """per-utterance inputs of a ragged call (a list of B tensors, or one padded tensor with B rows) -> list of B tensors"""
+        if isinstance(x, torch.Tensor):
+            x = [x[b] for b in range(B)]
+        assert len(x) == B, f"{what}: {len(x)} entries for {B} utterances"
+        return x
+
+    @torch.no_grad()
+    def decode_ragged(self, mels, sources, lengths: Optional[Sequence[int]] = None) -> List[torch.Tensor]:
+        """B utterances of different lengths through ONE launch sequence.  mels: list of (80, T_b) (or a padded (B, 80, T') tensor plus
+        ``lengths``); sources: list of (1, S_b) with S_b = T_b * total_upsample (or a padded (B, 1, S') / (B, S') tensor).  -> list of
+        (S_b,) waveforms, each what ``decode`` returns for that utterance alone (views of the (B, T) workspace, like ``decode``'s result)."""
+        ws, B, T, lens = self._ragged_inputs(mels, lengths)
+        up = self.cfg.total_upsample
+        s2 = ws["s"]
+        for b, sb in enumerate(self._ragged_rows(sources, B, "sources")):
+            n = lens[b] * up
+            sb = sb.reshape(-1)
+            assert sb.numel() >= n, f"source {b}: {sb.numel()} samples for {lens[b]} frames"
+            s2[b, :n].copy_(sb[:n])
+        wav = self._decode_cl(ws, B, T, s2, ragged=True)
+        return [wav[b, :lens[b] * up] for b in range(B)]
+
+    @torch.no_grad()
+    def inference_ragged(self, mels, cache_source=None, phase_vec=None, noise=None, lengths: Optional[Sequence[int]] = None):
+        """``inference`` (F0 -> source -> decode) of B utterances of different lengths in one pass.  mels as in ``decode_ragged``;
+        cache_source / phase_vec / noise: None or one entry per utterance of that utterance's own shape ((1, 1, n_b) / (1, nh, 1) /
+        (1, nh, S_b); a cache_source entry may be None or empty).  Randoms that are not injected are drawn on the device for the padded
+        shape.  -> (list of (S_b,) waveforms, list of (1, S_b) sources), views of the (B, T) workspace."""
+        ws, B, T, lens = self._ragged_inputs(mels, lengths)
+        cfg, dev = self.cfg, self.device
+        up, nh = cfg.total_upsample, cfg.nb_harmonics + 1
+        S = T * up
+        self._f0_from_cl(ws, B, T, lens=ws["lens_dev"])
+        if phase_vec is not None:
+            phase_vec = torch.stack([p.to(dev, torch.float32).reshape(nh) for p in self._ragged_rows(phase_vec, B, "phase_vec")])
+        if noise is not None:
+            if "noise_in" not in ws:
+                ws["noise_in"] = torch.empty(B, nh, S, device=dev, dtype=torch.float32)
+            for b, nz in enumerate(self._ragged_rows(noise, B, "noise")):
+                n = lens[b] * up
+                ws["noise_in"][b, :, :n].copy_(nz.reshape(nh, -1)[:, :n])
+            noise = ws["noise_in"]
+        s = self.source(ws["f0"], phase_vec, noise)
+        if cache_source is not None:
+            for b, c in enumerate(cache_source):
+                if c is not None and c.numel():
+                    s[b, :c.numel()] = c.to(dev, torch.float32).reshape(-1)
+        wav = self._decode_cl(ws, B, T, s, ragged=True)
+        return [wav[b, :lens[b] * up] for b in range(B)], [s[b:b + 1, :lens[b] * up] for b in range(B)]

@@ -84,6 +84,9 @@ class CosyVoice2Model:
         # flow CUs (622-631 vs 605-612 audio-s/s) — on 64 CUs a 32-row prefill stalls both token loops for ~0.1 s per job
         self.prefill_on_flow_cus = os.environ.get("CV_PREFILL_ON_FLOW", "1") != "0"
         self.pipeline_stats = None  # set to a list to collect (stage, batches, start, end) of every tts_batches job
+        # utterances of different generated lengths (free-running sampling): True = ONE ragged vocoder pass over the padded batch
+        # (HiFTGenerator.inference_ragged, exact per utterance); False = the per-utterance loop of batch-1 vocoder calls, kept as the cross-check
+        self.ragged_hift = True
 
     def _drop_contexts(self):
         """Forget every extra decode context (they share the weight tensors of the LM they were made from: after a reload they
@@ -407,8 +410,9 @@ class CosyVoice2Model:
 
     def _flow_hift(self, b, toks):
         """Flow + HiFT of one batch.  Equal generated lengths (teacher-forced runs, the benchmark): one batched pass ->
-        wav (B, S).  Free-running sampling ends every sequence at its own step: flow + HiFT then run per utterance (the
-        flow runs once over the ragged batch, HiFT per utterance) -> list of B waveforms (S_b,)."""
+        wav (B, S).  Free-running sampling ends every sequence at its own step: the flow and the vocoder then each run once over
+        the ragged batch (rows padded to the longest, every stage bounded by the row's own length: exact per utterance) -> list of
+        B waveforms (S_b,).  ``ragged_hift = False``: the vocoder runs per utterance instead (the cross-check)."""
         n = len(toks[0])
         zero = torch.zeros(1, 1, 0)
         if all(len(t) == n for t in toks):
@@ -416,9 +420,11 @@ class CosyVoice2Model:
             mel = self.flow.inference_batch(tok, b["flow_prompt_speech_tokens"], b["prompt_speech_feats"], b["flow_embeddings"])
             wav, _ = self.hift.inference(speech_feat=mel.contiguous(), cache_source=zero)
             return wav
-        # one batched flow pass over the ragged batch (rows padded to the longest, tails masked: exact), HiFT per utterance
-        # (its symmetric convolutions would see the padding)
         B = len(toks)
+        if self.ragged_hift:
+            mel, lens = self._flow_ragged(b, toks)
+            wavs, _ = self.hift.inference_ragged(mel, lengths=lens)
+            return [w.clone() for w in wavs]   # never hand out views of HiFT's per-shape workspace
         mels = self.flow.inference_ragged([torch.tensor(t, dtype=torch.int32) for t in toks],
                                           [b["flow_prompt_speech_tokens"][i] for i in range(B)],
                                           [b["prompt_speech_feats"][i] for i in range(B)], b["flow_embeddings"])
@@ -427,6 +433,13 @@ class CosyVoice2Model:
             wav, _ = self.hift.inference(speech_feat=mel.unsqueeze(0).contiguous(), cache_source=zero)
             outs.append(wav[0].clone())
         return outs
+
+    def _flow_ragged(self, b, toks):
+        """One flow pass over utterances of different generated lengths -> (padded left-aligned mel (B, 80, T) of its own, frame counts)."""
+        B = len(toks)
+        return self.flow.inference_ragged([torch.tensor(t, dtype=torch.int32) for t in toks],
+                                          [b["flow_prompt_speech_tokens"][i] for i in range(B)],
+                                          [b["prompt_speech_feats"][i] for i in range(B)], b["flow_embeddings"], padded=True)
 
     def _tts_batches_partitioned(self, batches, to_host, k, n_llm):
         import queue
@@ -487,20 +500,24 @@ class CosyVoice2Model:
                 return out
             return [(w, done) for w in torch.split(wav, counts, dim=0)] if len(counts) > 1 else [(wav, done)]
 
-        def hift_job(mel, mel_ready, t_job, counts):
-            """HiFT (+ D2H) of one equal-length flow group on its own stream over the flow CUs: the vocoder of group i fills the CUs the
+        def hift_job(mel, lens, mel_ready, t_job, counts):
+            """HiFT (+ D2H) of one flow group on its own stream over the flow CUs: the vocoder of group i fills the CUs the
             flow of group i + 1 leaves idle (the tail round of every attention launch, tile quantisation of the row-block
-            kernels) instead of extending the flow stream's critical path (17 of a 91 ms job on all CUs)."""
+            kernels) instead of extending the flow stream's critical path (17 of a 91 ms job on all CUs).  ``lens``: frame counts of a
+            ragged group (mel padded, one ragged vocoder pass) or None."""
             with torch.no_grad(), torch.cuda.stream(hift_part):
                 hift_part.wait_event(mel_ready)
                 mel.record_stream(hift_part)
-                wav, _ = self.hift.inference(speech_feat=mel, cache_source=torch.zeros(1, 1, 0))
+                if lens is None:
+                    wav, _ = self.hift.inference(speech_feat=mel, cache_source=torch.zeros(1, 1, 0))
+                else:
+                    wav, _ = self.hift.inference_ragged(mel, lengths=lens)
                 if to_host:
-                    res = split_rows(wav.cpu(), counts, None)
+                    res = split_rows([w.cpu() for w in wav] if lens is not None else wav.cpu(), counts, None)
                     if self.pipeline_stats is not None:
                         self.pipeline_stats.append(("flow", len(counts), t_job, time.perf_counter()))
                     return res
-                wav = wav.clone()
+                wav = [w.clone() for w in wav] if lens is not None else wav.clone()
                 done = torch.cuda.Event()
                 done.record(hift_part)
                 return split_rows(wav, counts, done)
@@ -530,19 +547,23 @@ class CosyVoice2Model:
             if est is not None:   # tile sizes of the row-block kernels (and the solver graph that bakes them in) follow the CUs of the stream
                 est.cu_budget = 0 if stream is flow_full else (32 - k) * 8
             n_t = len(toks[0])
-            if self.overlap_hift and all(len(t) == n_t for t in toks):
+            equal = all(len(t) == n_t for t in toks)
+            if self.overlap_hift and (equal or self.ragged_hift):
                 with torch.no_grad(), torch.cuda.stream(stream):
                     for r in ready_evs:
                         stream.wait_event(r)
                     stream.wait_stream(flow_part if stream is flow_full else flow_full)  # workspaces of the previous group
                     if b is None:
                         b = merged()
-                    tok = torch.tensor(toks, dtype=torch.int32, device=self.device)
-                    mel = self.flow.inference_batch(tok, b["flow_prompt_speech_tokens"], b["prompt_speech_feats"], b["flow_embeddings"])
-                    mel = mel.contiguous().clone()   # the flow's output buffer is rewritten by the next group
+                    if equal:
+                        tok = torch.tensor(toks, dtype=torch.int32, device=self.device)
+                        mel = self.flow.inference_batch(tok, b["flow_prompt_speech_tokens"], b["prompt_speech_feats"], b["flow_embeddings"])
+                        mel, lens = mel.contiguous().clone(), None   # the flow's output buffer is rewritten by the next group
+                    else:
+                        mel, lens = self._flow_ragged(b, toks)       # a padded tensor of its own
                     mel_ready = torch.cuda.Event()
                     mel_ready.record(stream)
-                return hift_pool.submit(hift_job, mel, mel_ready, t_job, counts)   # one worker: vocoder workspaces are used in group order
+                return hift_pool.submit(hift_job, mel, lens, mel_ready, t_job, counts)   # one worker: vocoder workspaces are used in group order
             with torch.no_grad(), torch.cuda.stream(stream):
                 for r in ready_evs:
                     stream.wait_event(r)

@@ -109,8 +109,11 @@ def _issue(name, p):
 def gemm(A, W, M, N, K, *, dtype=None, batch=1, batch_inner=0, a_bs=(0, 0), lda=None, a_rows=0, cin=0,
          a_row_stride=1, tap_base=0, tap_step=0, w_bs=(0, 0), ldw=None, bias=None, res=None, res_bs=(0, 0), ldres=0,
          res2=None, ldres2=0, out_scale=1.0, act=ACT_NONE, act_param=None, act_slope=0.0, out_f32=None, o32_bs=(0, 0),
-         ldo32=0, out_act=None, oa_bs=(0, 0), ldoa=0, out_row_stride=1, out_row_off=0, out_rows=0, qkv=None, x3_flags=0):
-    _req_cuda(A, W, bias, res, res2, out_f32, out_act)
+         ldo32=0, out_act=None, oa_bs=(0, 0), ldoa=0, out_row_stride=1, out_row_off=0, out_rows=0, qkv=None, x3_flags=0,
+         lens=None, a_len=(0, 0), m_len=(0, 0)):
+    """``lens`` (device int32 (batch,), off by default) makes the launch ragged (cv_gemm_params.len_base): batch z reads zeros past its
+    own ``lens[z] * a_len[0] + a_len[1]`` rows of A and only its first ``lens[z] * m_len[0] + m_len[1]`` output rows are needed."""
+    _req_cuda(A, W, bias, res, res2, out_f32, out_act, lens)
     p = L.GemmParams()
     p.dtype = L.TORCH_DT[A.dtype] if dtype is None else dtype
     if dtype is None and A.dtype == torch.float32 and getattr(_tls, "f32_mode", "exact") == "bf16x3":
@@ -127,6 +130,10 @@ def gemm(A, W, M, N, K, *, dtype=None, batch=1, batch_inner=0, a_bs=(0, 0), lda=
     p.out_act, p.oa_bs0, p.oa_bs1, p.ldoa = L.ptr(out_act), oa_bs[0], oa_bs[1], ldoa
     p.out_row_stride, p.out_row_off, p.out_rows = out_row_stride, out_row_off, out_rows
     p.x3_flags = x3_flags if p.dtype == L.CV_F32X3 else 0   # pre-split operand / output storage of the bf16x3 path (cv_gemm_params.x3_flags)
+    if lens is not None:
+        assert lens.dtype == torch.int32 and lens.is_contiguous() and lens.numel() >= batch
+        p.len_base = lens.data_ptr()
+        (p.a_len_mul, p.a_len_add), (p.m_len_mul, p.m_len_add) = a_len, m_len
     if qkv is not None:
         p.out_mode = OUT_QKV
         p.q_cols, p.k_cols, p.q_scale = qkv["q_cols"], qkv["k_cols"], qkv.get("q_scale", 1.0)

@@ -38,7 +38,8 @@ const char* cv_arch(void); /* "gfx950" */
  * cv_gemm — C[z][m][n] = epilogue( sum_k A[z][row(m,k)][ci(k)] * W[n][k] ), MFMA, fp32 accumulate.
  * One kernel family for every Linear and Conv1d/ConvTranspose1d on the path (channels-last
  * activations, implicit im2col: k = tap*cin + ci, A row = m*a_row_stride + tap_base + tap*tap_step,
- * rows outside [0,a_rows) read as zero = the conv padding).
+ * rows outside [0,a_rows) read as zero = the conv padding; with `len_base` set the bound is per batch index, see the
+ * struct's last fields: a padded batch of sequences of different lengths then convolves every sequence as if it were alone).
  * Replaces: torch.nn.Linear / Conv1d / ConvTranspose1d calls of
  *   cosyvoice/flow/decoder.py:36-85,222-334, flow/components/transformer.py:243-316,
  *   transformer/attention.py:69-76, transformer/positionwise_feed_forward.py:47-56,
@@ -72,6 +73,13 @@ typedef struct cv_gemm_params {
    * bit 0: A is pre-split; bit 1: W is pre-split (both or neither); bit 2: out_act is WRITTEN pre-split (row-major, N % 8 == 0).
    * Results are bit-identical to the plain CV_F32X3 launch. */
   int32_t x3_flags; int32_t reserved_x3;
+  /* RAGGED batches (all zero / NULL = off, the behaviour above).  len_base: DEVICE int32 [batch], a base length per batch index z (read by the
+   * kernel, so a captured graph serves any lengths).  A rows at or past  a_len(z) = min(a_rows, len_base[z]*a_len_mul + a_len_add)  read as
+   * zero whatever the buffer holds there (a_len_mul = a_len_add = 0: a_len = a_rows);  only the first  m_len(z) = len_base[z]*m_len_mul +
+   * m_len_add  of the M rows are needed: a workgroup whose rows all lie at or past m_len(z) returns without touching memory, rows past
+   * m_len(z) inside a live tile may still be stored (m_len_mul = m_len_add = 0: m_len = M).  Addresses are clamped with a_rows / M, never with
+   * the device values.  Needs batch_inner == batch and CV_OUT_ROWMAJOR; not taken by the opt-in window kernel (CV_CONV_WIN). */
+  const int32_t* len_base; int32_t a_len_mul, a_len_add, m_len_mul, m_len_add;
 } cv_gemm_params;
 int cv_gemm(const cv_gemm_params* p, void* stream);
 
@@ -533,7 +541,13 @@ int cv_flow_euler_graph_destroy(void* graph);
  * Every conv is a cv_gemm launch over channels-last tensors with the activation / residual / mean fused into its epilogue.
  * `dtype` = element type of the activation tensors and weights (CV_F32 for the reference-exact vocoder); `gemm_dtype` = what
  * cv_gemm multiplies in (CV_F32 exact, CV_F32X3 = bf16 hi/lo split products, or the 16-bit dtype).
- * `stages`, every `units` / `rbs` / `phases` / `xa` array are HOST arrays read at enqueue / capture time only. */
+ * `stages`, every `units` / `rbs` / `phases` / `xa` array are HOST arrays read at enqueue / capture time only.
+ * RAGGED batches: `lens` (DEVICE int32 [B], frames T_b <= T of each utterance, NULL = all T) makes row b of the padded batch compute
+ * exactly what a batch-1 decode of its first T_b frames computes: every conv / phase GEMM reads zeros past the utterance's own length at
+ * that stage (cv_gemm_params.len_base) and skips the row tiles past it, the source STFT reflects at S_b = T_b * S / T and the iSTFT
+ * normalises and ends at its own last frame.  wav[b][0 .. S_b) is the result; what lies past it (and past the per-stage lengths in the
+ * workspace) is unspecified.  The lengths are read on the device: one descriptor / one captured graph per (B, T) serves any lengths.
+ * Needs S == T * prod(u) * hop and stages[i].t_out == T * prod(u[0..i]) (+ 1 on the last stage). */
 typedef struct cv_hift_conv {        /* channels-last Conv1d: w [cout][k*cin] with k index = tap*cin + ci; cin = channel pitch of its input */
   const void* w; const float* b; int32_t k, cin, cout, dilation, pad_left, stride;
   int32_t x3_flags, reserved;        /* gemm_dtype CV_F32X3: cv_gemm_params.x3_flags of this conv (bit 2 is dropped when it has no 16/32-bit activation output) */
@@ -561,6 +575,7 @@ typedef struct cv_hift_decode_desc {
   void* a_pre;                       /* [B][T][conv_pre.cout] `dtype` */
   float* post;                       /* [B][t_last][stft_ld] fp32 */
   float* wav;                        /* [B][(t_last - 1) * hop] fp32 output */
+  const int32_t* lens;               /* ragged batches: DEVICE int32 [B], 1 <= T_b <= T; NULL = every utterance has T frames */
 } cv_hift_decode_desc;
 int cv_sizeof_hift_decode_desc(void);
 int cv_sizeof_hift_stage(void);
