@@ -403,7 +403,11 @@ int cv_rope_append(const float* qkv, int32_t ldqkv, const int32_t* pos_base, int
  * (= [q | k | v], position ctx_len[b]; inv_freq is then the table rope[ctx_max][64] = [cos 32 | sin 32] per position),
  * appends K / V^T of its kv head to the caches, then attends (ctx_add = 1).  In the fused form BOTH caches are
  * FRAGMENT-TILED (cv_kv_retile below): per (sequence, kv head) ctx_max/64 tiles of 64 keys x 64 d in MFMA operand order, so every
- * fragment load is 64 lanes x 16 contiguous bytes; the un-fused form reads the row-major caches cv_rope_append writes. */
+ * fragment load is 64 lanes x 16 contiguous bytes; the un-fused form reads the row-major caches cv_rope_append writes.
+ * Precondition: both caches hold FINITE values in all ctx_max slots of every (sequence, kv head), also past the context (zero-initialise
+ * them): whole 64-key tiles are loaded and the keys beyond the context meet a probability of exactly 0, which only a finite value survives.
+ * ctx_len[b] + ctx_add > ctx_max attends to the ctx_max cached keys; in the fused form ctx_len[b] >= ctx_max means there is no slot for the
+ * new token: nothing is appended, both caches stay unchanged, and the output row is finite but otherwise unspecified. */
 int cv_decode_attention(const void* q, int32_t ldq, const void* kcache, const void* vtcache, const int32_t* ctx_len,
                         int32_t ctx_add, void* out, int32_t ldo, int32_t B, int32_t Hq, int32_t Hkv, int32_t ctx_max,
                         float scale, int32_t dtype, const float* qkv, int32_t ldqkv, const float* inv_freq, void* stream);

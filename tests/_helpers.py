@@ -116,3 +116,154 @@ def scan_drift_bound(cfg, f0_up, nh=None):
     F_top = f0_up * torch.tensor(float(nh)) / cfg.sampling_rate
     c_max = torch.cumsum(F_top, dim=-1).max()
     return 2 * math.pi * cfg.nsf_alpha * ulp(c_max, torch.float32).item(), c_max.item()
+
+
+# ----------------------------------------------------------------------------- attention (cv_attention, cv_decode_attention)
+LOG2E32 = 1.4426950408889634
+NEG_BIG = -1e30
+ATTN_CS = 136           # score term of attn_bound, see its docstring
+ATTN_C = 10             # constant term of attn_bound
+DECODE_MERGE_C = 10     # the 8-wave log-sum-exp merge of cv_decode_attention
+
+
+def attn_mask(B, Tq, Tk, klen=None, chunk=0, causal=False, causal_off=0, q_off=0):
+    """(B, Tq, Tk) bool, True = visible, as include/cosyvoice_amd.h states the masks: j < min(klen[b], Tk); chunk: j < ((i + q_off) / chunk
+    + 1) * chunk; causal: j <= i + causal_off."""
+    i = torch.arange(Tq)[:, None]
+    j = torch.arange(Tk)[None, :]
+    ok = torch.ones(Tq, Tk, dtype=torch.bool)
+    if causal:
+        ok &= j <= i + causal_off
+    if chunk:
+        ok &= j < ((i + q_off) // chunk + 1) * chunk
+    ok = ok[None].expand(B, Tq, Tk).clone()
+    if klen is not None:
+        kl = torch.as_tensor(klen, dtype=torch.long).clamp(max=Tk)
+        ok &= j[None] < kl[:, None, None]
+    return ok
+
+
+def attn_ref64(q, k, v, scale, ok, bias=None):
+    """float64 softmax(scale q k^T + bias) v over the visible keys, from the already rounded operands.  q (B, H, Tq, 64), k / v (B, Hkv, Tk, 64),
+    ok (B, Tq, Tk) bool, bias (B, H, Tq, Tk) or None (its masked entries may hold anything, NaN included).  Rows without a visible key are zero.
+    Returns ref, A = sum_j p |v|, S = max over the visible keys of scale sum_d |q k| + |bias| (B, H, Tq), and sub = sum_j [p / max p < 2^-14]
+    p |v| (the part of A carried by probabilities that are subnormal in fp16)."""
+    q, k, v = q.double(), k.double(), v.double()
+    rep = q.shape[1] // k.shape[1]
+    k, v = k.repeat_interleave(rep, 1), v.repeat_interleave(rep, 1)
+    okh = ok[:, None]
+    s = scale * (q @ k.transpose(-1, -2))
+    sa = scale * (q.abs() @ k.abs().transpose(-1, -2))
+    if bias is not None:
+        bz = torch.where(okh, bias.double(), torch.zeros((), dtype=torch.float64))
+        s, sa = s + bz, sa + bz.abs()
+    s = s.masked_fill(~okh, float("-inf"))
+    live = okh.any(-1, keepdim=True)
+    m = torch.where(live, s.max(-1, keepdim=True).values, torch.zeros((), dtype=torch.float64))
+    e = torch.exp(s - m)                                                   # 1 at the row maximum, 0 at masked keys
+    p = e / e.sum(-1, keepdim=True).clamp_min(1e-300)
+    S = torch.where(live[..., 0], sa.masked_fill(~okh, 0.0).max(-1).values, torch.zeros((), dtype=torch.float64))
+    return p @ v, p @ v.abs(), S, (p * (e < 2.0 ** -14)) @ v.abs()
+
+
+def attn_bound(ref, A, S, sub, Tk, dt, merge=0):
+    """Element-wise bound of the flash kernels against attn_ref64 (derivation: module docstring of tests/test_attention_ops_gpu.py):
+    (u_P + ATTN_CS 2^-23 S_i + (Tk + 2 ceil(Tk / 64) + ATTN_C + merge) 2^-23) A_id + half an ulp of the output (+ sub for fp16).  Tk: the
+    number of keys a row may see, an int or an integer tensor that broadcasts against A."""
+    n = Tk + 2 * ((Tk + 63) // 64) + ATTN_C + merge
+    b = (2.0 ** -(MANT[dt] + 1) + ATTN_CS * EPS32 * S[..., None] + n * EPS32) * A + 0.5 * ulp(ref, dt)
+    return b + sub if dt == torch.float16 else b
+
+
+def attn_emulate(q, k, v, scale, ok, dt, bias=None, waves=1, flush=False):
+    """Plain torch emulation of the kernels' arithmetic (no library code): fp32 scores, scale * log2(e) folded into one fp32 factor, masked
+    scores = -1e30, 64-key online softmax with exp2, the denominator from the unrounded fp32 P, the numerator from P rounded to ``dt``
+    (flush: fp16-subnormal P flushed to zero instead of rounded gradually), fp32 accumulation, rows without a visible key zero; ``waves``
+    > 1: tile t belongs to wave t % waves and the waves are merged by log-sum-exp (cv_decode_attention).  Returns (B, H, Tq, 64) ``dt``."""
+    f32 = torch.float32
+    rep = q.shape[1] // k.shape[1]
+    qf, kf, vf = q.to(f32), k.to(f32).repeat_interleave(rep, 1), v.to(f32).repeat_interleave(rep, 1)
+    Tk = kf.shape[2]
+    sc = (torch.tensor(scale, dtype=f32) * torch.tensor(LOG2E32, dtype=f32)).item()
+    t = (qf @ kf.transpose(-1, -2)) * sc
+    okh = ok[:, None].expand_as(t)
+    if bias is not None:
+        t = t + torch.where(okh, bias.to(f32), torch.zeros((), dtype=f32)) * torch.tensor(LOG2E32, dtype=f32)
+    t = torch.where(okh, t, torch.full((), NEG_BIG, dtype=f32))
+    shape = t.shape[:-1]
+    parts = []
+    for w in range(waves):
+        m, l, o = torch.full(shape, NEG_BIG, dtype=f32), torch.zeros(shape, dtype=f32), torch.zeros(*shape, 64, dtype=f32)
+        for j0 in range(64 * w, Tk, 64 * waves):
+            tt = t[..., j0:j0 + 64]
+            mnew = torch.maximum(m, tt.max(-1).values)
+            p = torch.exp2(tt - mnew[..., None])
+            p = torch.where((mnew <= 0.5 * NEG_BIG)[..., None], torch.zeros((), dtype=f32), p)
+            alpha = torch.exp2(m - mnew)
+            l = l * alpha + p.sum(-1)
+            pr = p.to(dt)
+            if flush and dt == torch.float16:
+                pr = torch.where(p < 2.0 ** -14, torch.zeros((), dtype=dt), pr)
+            o = o * alpha[..., None] + pr.to(f32) @ vf[..., j0:j0 + 64, :]
+            m = mnew
+        parts.append((m, l, o))
+    if waves > 1:
+        mm = torch.stack([p_[0] for p_ in parts]).max(0).values
+        l, o = torch.zeros(shape, dtype=f32), torch.zeros(*shape, 64, dtype=f32)
+        for m_, l_, o_ in parts:
+            ww = torch.exp2(m_ - mm)
+            l, o = l + l_ * ww, o + o_ * ww[..., None]
+    inv = torch.where(l > 0, 1.0 / l.clamp_min(1e-38), torch.zeros((), dtype=f32))
+    return (o * inv[..., None]).to(dt)
+
+
+def kv_tile_index(key, d, v=False):
+    """Vectorised index map of the fragment-tiled KV cache as include/cosyvoice_amd.h documents it (cv_kv_retile), written from the header's
+    formulas, not from ops.kv_tile_index: element offset of (key, d) inside one (sequence, kv head) cache; key, d integer tensors."""
+    t, r = key // 64, key % 64
+    if not v:       # ((kt*2 + f)*64 + lq + 16*lg)*8 + e : key 16*kt + lq, d = 32*f + 8*lg + e
+        kt, lq, f, lg, e = r // 16, r % 16, d // 32, (d % 32) // 8, d % 8
+        i = ((kt * 2 + f) * 64 + lq + 16 * lg) * 8 + e
+    else:           # ((dt*2 + s2)*64 + lq + 16*lg)*8 + e : key 32*s2 + 16*(e >> 2) + 4*lg + (e & 3), d = 16*dt + lq
+        dt_, lq, s2, r32 = d // 16, d % 16, r // 32, r % 32
+        e = 4 * (r32 // 16) + r32 % 4
+        lg = (r32 % 16) // 4
+        i = ((dt_ * 2 + s2) * 64 + lq + 16 * lg) * 8 + e
+    return t * 4096 + i
+
+
+# ----------------------------------------------------------------------------- LLM decode ops
+def rope_ref64(x, ang32):
+    """HF rotate_half RoPE of x (.., 64) in float64 with the angle given in fp32 (.., 32) (the single fp32 product pos * inv_freq[d], or a table
+    entry): returns ref, sum|terms| and torch's own fp32 evaluation of the same expression."""
+    x1, x2 = x[..., :32].double(), x[..., 32:].double()
+    c, s = torch.cos(ang32.double()), torch.sin(ang32.double())
+    ref = torch.cat([x1 * c - x2 * s, x2 * c + x1 * s], -1)
+    sabs = torch.cat([(x1 * c).abs() + (x2 * s).abs(), (x2 * c).abs() + (x1 * s).abs()], -1)
+    c32, s32 = torch.cos(ang32), torch.sin(ang32)
+    t32 = torch.cat([x[..., :32] * c32 - x[..., 32:] * s32, x[..., 32:] * c32 + x[..., :32] * s32], -1)
+    return ref, sabs, t32
+
+
+def rope_table_ref64(x, c32, s32):
+    """The same rotation with cos / sin given as fp32 numbers (a table row), taken as exact: ref and sum|terms|."""
+    x1, x2, c, s = x[..., :32].double(), x[..., 32:].double(), c32.double(), s32.double()
+    return (torch.cat([x1 * c - x2 * s, x2 * c + x1 * s], -1),
+            torch.cat([(x1 * c).abs() + (x2 * s).abs(), (x2 * c).abs() + (x1 * s).abs()], -1))
+
+
+def rope_bound(ref, sabs, t32, dt):
+    """Rule 2 with n = 2 (two products, one sum) + rule 3 for sincosf (4 x max(e32, 2^-23 |ref|), e32 from torch's fp32 evaluation) + half an
+    ulp of the 16-bit output (inside sum_bound)."""
+    e32 = (t32.double() - ref).abs().max()
+    return sum_bound(2, sabs, ref, dt) + 4.0 * torch.maximum(e32, EPS32 * ref.abs())
+
+
+def rmsnorm_ref64(v, gamma, eps, dt):
+    """rmsnorm(v) * gamma in float64 from fp32 v (rows, dim), and its bound: the sum of dim squares in fp32 errs by <= (dim + 2) 2^-23 of
+    itself (all terms >= 0), / dim and + eps add two roundings; through rsqrt (d x^-1/2 = -x^-3/2 dx / 2) that is (dim + 4) / 2 x 2^-23
+    relative, rsqrtf itself <= 2 ulp, the two products v * rstd * gamma one more: (dim / 2 + 5) 2^-23 |ref| + half an ulp of the output."""
+    v, g = v.double(), gamma.double()
+    dim = v.shape[-1]
+    ref = v * torch.rsqrt((v * v).mean(-1, keepdim=True) + torch.tensor(eps, dtype=torch.float32).double()) * g
+    return ref, (dim / 2 + 5) * EPS32 * ref.abs() + 0.5 * ulp(ref, dt)

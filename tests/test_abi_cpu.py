@@ -90,17 +90,18 @@ def test_version_and_unbound_entry_points_reject_null_arguments():
 # test of their own (aliases of tested entry points, and the eager *_enqueue forms of stages that the tests run through *_graph_create).
 # A new export fails test_every_export_has_a_test_module until somebody decides where it is tested.
 _HELPERS, _GRAPH = "test_helper_kernels_gpu", ("test_flow_gpu", "use_graph = True")
+_LLM_OPS = "test_llm_ops_gpu"
 COVERAGE = {
     "cv_version": "test_abi_cpu", "cv_arch": "test_abi_cpu",
-    "cv_gemm": "test_gemm_modes_gpu", "cv_layernorm": "test_gemm_gpu", "cv_attention": "test_attention_gpu",
+    "cv_gemm": "test_gemm_modes_gpu", "cv_layernorm": "test_gemm_gpu", "cv_attention": "test_attention_ops_gpu",
     "cv_sizeof_gemm_params": "lifecycle", "cv_sizeof_norm_params": "lifecycle", "cv_sizeof_attn_params": "lifecycle",
     "cv_to_channels_last": _HELPERS, "cv_to_channels_first": _HELPERS, "cv_snake_multi": _HELPERS, "cv_stft16": _HELPERS,
     "cv_istft16": _HELPERS, "cv_hift_source": _HELPERS, "cv_embedding": _HELPERS, "cv_est_pack": _HELPERS, "cv_cfm_update": _HELPERS,
     "cv_graph_begin": _GRAPH, "cv_graph_end": _GRAPH, "cv_graph_launch": _GRAPH, "cv_graph_destroy": "lifecycle",
     "cv_graph_launch_direct": ("test_model_gpu", "cu_partition"), "cv_graph_num_launches": ("test_speaker_gpu", "num_launches"),
     "cv_stream_create_cumask": ("test_model_gpu", "cu_partition"), "cv_stream_destroy": "lifecycle",
-    "cv_skinny_gemm": "test_llm_gpu", "cv_pack_skinny": "test_llm_gpu", "cv_rmsnorm_reduce": "test_llm_gpu", "cv_rope_append": "test_llm_gpu",
-    "cv_decode_attention": "test_llm_gpu", "cv_kv_retile": "test_llm_gpu", "cv_sample_ras": "test_llm_gpu",
+    "cv_skinny_gemm": _LLM_OPS, "cv_pack_skinny": _LLM_OPS, "cv_rmsnorm_reduce": _LLM_OPS, "cv_rope_append": _LLM_OPS,
+    "cv_decode_attention": _LLM_OPS, "cv_kv_retile": _LLM_OPS, "cv_sample_ras": "test_llm_gpu",
     "cv_sizeof_skinny_params": "lifecycle", "cv_sizeof_sample_params": "lifecycle",
     "cv_anti_alias_act": "test_bigvgan_gpu", "cv_anti_alias_act_cl": "test_bigvgan_gpu",
     "cv_stft_magnitude": _HELPERS, "cv_log_clamp_channels_first": _HELPERS,
