@@ -36,7 +36,7 @@ class GemmParams(C.Structure):
         ("q_cols", _i32), ("k_cols", _i32), ("q_scale", _f32),
         ("k_out", _vp), ("k_bs", _i64), ("ldk", _i32),
         ("vt_out", _vp), ("vt_heads", _i32), ("vt_ld", _i32),
-        ("x3_flags", _i32), ("reserved_x3", _i32),
+        ("x3_flags", _i32), ("conv_win", _i32),
         ("len_base", _vp), ("a_len_mul", _i32), ("a_len_add", _i32), ("m_len_mul", _i32), ("m_len_add", _i32),
     ]
 
@@ -77,6 +77,7 @@ class AttnParams(C.Structure):
         ("klen", _vp), ("chunk", _i32), ("causal", _i32), ("causal_off", _i32),
         ("bias", _vp), ("bias_bs", _i64), ("bias_hs", _i64), ("bias_ld", _i32), ("q_off", _i32),
         ("q_hs", _i64), ("k_hs", _i64),
+        ("mfma", _i32), ("waves", _i32),
     ]
 
 
@@ -110,7 +111,7 @@ class TBlockParams(C.Structure):
         ("g3", _vp), ("b3n", _vp),
         ("w1_p", _vp), ("bf1", _vp),
         ("w2_p", _vp), ("bf2", _vp),
-        ("out_act", _vp), ("ldoa", _i32), ("cus", _i32),
+        ("out_act", _vp), ("ldoa", _i32), ("cus", _i32), ("mt", _i32),
     ]
 
 
@@ -123,7 +124,7 @@ class ResblockParams(C.Structure):
         ("w2_p", _vp), ("b2", _vp), ("g2", _vp), ("be2", _vp),
         ("wr_p", _vp), ("br", _vp),
         ("out", _vp), ("ldo", _i32),
-        ("eps", _f32), ("cus", _i32),
+        ("eps", _f32), ("cus", _i32), ("mt", _i32),
     ]
 
 
@@ -208,7 +209,7 @@ class FlowSolverDesc(C.Structure):
 
 class HiftConv(C.Structure):
     _fields_ = [("w", _vp), ("b", _vp), ("k", _i32), ("cin", _i32), ("cout", _i32), ("dilation", _i32), ("pad_left", _i32), ("stride", _i32),
-                ("x3_flags", _i32), ("reserved", _i32)]
+                ("x3_flags", _i32), ("conv_win", _i32)]
 
 
 class HiftResunit(C.Structure):

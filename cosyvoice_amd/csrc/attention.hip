@@ -8,7 +8,6 @@
 //   * V arrives pre-transposed (V^T [d][key], written by the QKV producer), so its A fragment is ONE 16-byte
 //     LDS read per lane from a [64 d][128 B] image with XOR-swizzled 16-byte chunk slots.
 // K / V^T tiles (64 keys) are staged through LDS, double-buffered with register prefetch (one barrier per tile).
-#include <cstdlib>
 #include <type_traits>
 #include "cv_device.h"
 
@@ -359,7 +358,7 @@ __device__ __forceinline__ f32x16_t mfma32(const uint4& a, const uint4& b, f32x1
   else return __builtin_amdgcn_mfma_f32_32x32x16_f16(bitcast<f16x8_t>(a), bitcast<f16x8_t>(b), c, 0, 0, 0);
 }
 
-template <int DT, int NWV, int ABL = 0>   // ABL: timing-only ablations (CV_ATTN_ABL; wrong results): 1 no K/V tile traffic after tile 0, 2 no softmax arithmetic
+template <int DT, int NWV, int ABL = 0>   // ABL: timing-only ablations (wrong results; instantiated by hand for a measurement, DESIGN.md §6 Round 3, "Timing ablations of form (i)"): 1 no K/V tile traffic after tile 0, 2 no softmax arithmetic
 __global__ __launch_bounds__(64 * NWV, NWV == 4 ? 3 : 2) void attn32_kernel(const cv_attn_params p) {
   constexpr int NT = 64 * NWV, QW = 32 * NWV, NL = 512 / NT;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -944,22 +943,21 @@ extern "C" int cv_attention(const cv_attn_params* pp, void* stream) {
   if (p.vt_ld < p.Tk) return CV_ERR_ARG;
   if ((int64_t)p.Tk * p.ldk * 2 >= (int64_t)1 << 31 || (int64_t)64 * p.vt_ld * 2 >= (int64_t)1 << 31) return CV_ERR_UNSUPPORTED;   // 32-bit buffer offsets per (batch, head)
   if (((uintptr_t)p.q & 15) || ((uintptr_t)p.k & 15) || ((uintptr_t)p.vt & 15) || ((uintptr_t)p.out & 7)) return CV_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  const size_t lds = 2 * STAGE_BYTES;
-  // 64-query workgroups when 128-query ones would not even fill the chip once (CV_ATTN_WAVES=2|4 overrides: tuning aid)
-  const char* fe = getenv("CV_ATTN_WAVES");   // read per call: tests switch it
-  const int forced = fe ? atoi(fe) : 0;
-  const int64_t wgs4 = (int64_t)p.H * ((p.Tq + 127) / 128) * p.B;
-  const bool two = forced == 2 || (forced != 4 && wgs4 < 256);
-  // CV_ATTN_MFMA selects the alternative forms built and measured in round 3 (all tested against torch, tests/test_attention_gpu.py):
-  //   16 (default) the 16x16x32 form above;
+  // p.mfma selects among the three forms (all tested against torch, tests/test_attention_gpu.py):
+  //   0 / 16 the 16x16x32 form above (the library's choice);
   //   32 the same tiling on 32x32x16 MFMAs (half the MFMA issue slots, one cross-lane step per row max): 58.2 vs 57.0 us;
   //   64 64 queries per wave, K / V^T by LDS-DMA into a 3-stage ring, the softmax of one query block issued between the MFMAs of the
   //      other (no bias operand): 57.0 - 58.2 us.
   // At the estimator's batch-8 shape (16 x 8 heads x T = 1000) all three take 57 - 58 us: the time is ~410 VALU + 32 MFMA issued per 64
   // queries x 64 keys (SQ_INSTS_VALU identical in every form) and ~30 % of wave cycles waiting, not the tile schedule.
-  const char* me = getenv("CV_ATTN_MFMA");
-  const int mf = me ? atoi(me) : 0;
+  const int mf = p.mfma;
+  if (mf != 0 && mf != 16 && mf != 32 && mf != 64) return CV_ERR_ARG;
+  if (p.waves != 0 && p.waves != 2 && p.waves != 4) return CV_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t lds = 2 * STAGE_BYTES;
+  // 64-query workgroups when 128-query ones would not even fill the chip once (p.waves = 2 | 4 overrides: tuning aid)
+  const int64_t wgs4 = (int64_t)p.H * ((p.Tq + 127) / 128) * p.B;
+  const bool two = p.waves == 2 || (p.waves != 4 && wgs4 < 256);
   if (!p.bias && p.Tk >= 8 && p.vt_ld >= 8 && mf == 64) {
     dim3 grid(p.H, (p.Tq + 255) / 256, p.B);
     const size_t lds64 = 3 * STAGE_BYTES;
@@ -981,12 +979,7 @@ extern "C" int cv_attention(const cv_attn_params* pp, void* stream) {
   } else {
     dim3 grid(p.H, (p.Tq + 127) / 128, p.B);
     if (m32) {
-      const char* ae = getenv("CV_ATTN_ABL");
-      const int abl = ae ? atoi(ae) : 0;
-      if (abl == 1 && p.dtype == CV_F16) hipLaunchKernelGGL((attn32_kernel<CV_F16, 4, 1>), grid, dim3(256), lds, st, p);
-      else if (abl == 2 && p.dtype == CV_F16) hipLaunchKernelGGL((attn32_kernel<CV_F16, 4, 2>), grid, dim3(256), lds, st, p);
-      else if (abl == 3 && p.dtype == CV_F16) hipLaunchKernelGGL((attn32_kernel<CV_F16, 4, 3>), grid, dim3(256), lds, st, p);
-      else if (p.dtype == CV_BF16) hipLaunchKernelGGL((attn32_kernel<CV_BF16, 4>), grid, dim3(256), lds, st, p);
+      if (p.dtype == CV_BF16) hipLaunchKernelGGL((attn32_kernel<CV_BF16, 4>), grid, dim3(256), lds, st, p);
       else hipLaunchKernelGGL((attn32_kernel<CV_F16, 4>), grid, dim3(256), lds, st, p);
     } else {
       if (p.dtype == CV_BF16) hipLaunchKernelGGL((attn_kernel<CV_BF16, 4>), grid, dim3(256), lds, st, p);

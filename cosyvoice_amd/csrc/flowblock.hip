@@ -35,7 +35,7 @@
 // bookkeeping of the prefetched loads conservative.
 #include "cv_device.h"
 #include <climits>
-#include <cstdlib>
+#include <type_traits>
 
 namespace {
 
@@ -289,7 +289,7 @@ __device__ __forceinline__ void head_body(const cv_tblock_params& p, const char*
   }
 }
 
-template <int DT, int MT, int ABL = 0>   // ABL: timing-only ablations (1: no output stores, 2: no ring refills)
+template <int DT, int MT, int ABL = 0>   // ABL: timing-only ablations, wrong results, instantiated by hand for a measurement ("Timing ablations"; 1: no output stores, 2: no ring refills)
 __global__ __launch_bounds__(NTHR, 2) void tblock_head_kernel(const cv_tblock_params p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -326,7 +326,7 @@ __device__ __forceinline__ void ln_acc(f32x4_t (&acc)[MT][2], float* red, const 
 // image, and the [Q | K | V^T] GEMM of head_body runs on it — the last FFN refills of the register ring already fetch the head's first
 // weight groups.  One launch and one 1 KB-per-row read of x less per block; the head fields of the parameter block (g1, b1n, wqkv_p, qk,
 // vt) then describe block i + 1.  LDS: two more staged vectors (g1 | b1n) behind the four of the tail.
-template <int DT, bool OUTPROJ, int MT, int ABL = 0, bool NEXT = false>   // ABL: timing-only ablations (1: GELU -> identity, 2: no ring refills)
+template <int DT, bool OUTPROJ, int MT, int ABL = 0, bool NEXT = false>   // ABL: timing-only ablations, wrong results, instantiated by hand for a measurement ("Timing ablations"; 1: GELU -> identity, 2: no ring refills)
 __global__ __launch_bounds__(NTHR, 2) void tblock_tail_kernel(const cv_tblock_params p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* ximg = smem;
@@ -846,11 +846,9 @@ __global__ __launch_bounds__(NTHR, 2) void resblock_kernel(const cv_resblock_par
 int check_common(const cv_tblock_params& p) {
   if (p.dtype != CV_BF16 && p.dtype != CV_F16) return CV_ERR_UNSUPPORTED;
   if (p.C != TB_C || p.inner != TB_INNER || p.ff != TB_FF) return CV_ERR_UNSUPPORTED;
-  if (p.R <= 0 || p.T <= 0 || !p.x || (p.ldx & 3) || ((uintptr_t)p.x & 15)) return CV_ERR_ARG;
+  if (p.R <= 0 || p.T <= 0 || !p.x || (p.ldx & 3) || ((uintptr_t)p.x & 15) || p.mt < 0 || p.mt > 4) return CV_ERR_ARG;
   return CV_OK;
 }
-
-int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
 
 template <typename K>
 void set_lds(K kern, size_t lds) { hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); }
@@ -875,59 +873,41 @@ void launch_head(const cv_tblock_params& p, hipStream_t st) {
 // 15.6 / 19.0 / 23.1 / 27.3 us for MT = 1 / 2 / 3 / 4, i.e. about 9.4 + 2.8 MT and 11.7 + 3.9 MT).  At the
 // batch-8 shapes (R = 16, T = 1000: 256 or 336 workgroups) it reproduces the r02 choice (64 rows on the whole chip, 48 on 192 CUs);
 // at batch 1 (R = 2) it picks 16-row tiles (126 workgroups instead of 32 on 256 CUs).  p.cus = 0 means the whole chip.
-// CV_TBLOCK_MT=1..4 overrides (tuning aid, read per call: tests switch it).
+// mt = 1..4 (the params' own `mt` field) overrides: tuning aid; the entry points reject anything else but 0.
 constexpr int MT_FIXED = 3;
-int pick_mt(const cv_tblock_params& p) {
-  const int forced = env_int("CV_TBLOCK_MT", 0);
-  if (forced >= 1 && forced <= 4) return forced;
-  const int cus = p.cus > 0 ? p.cus : 256;
+int pick_mt(int R, int T, int cus, int mt) {
+  if (mt != 0) return mt;
+  if (cus <= 0) cus = 256;
   int best = 4;
   int64_t best_cost = INT64_MAX;
-  for (int mt = 4; mt >= 1; --mt) {   // ties go to the larger tile (fewer weight re-reads)
-    const int wgs = p.R * ((p.T + 16 * mt - 1) / (16 * mt));
-    const int64_t cost = (int64_t)((wgs + cus - 1) / cus) * (mt + MT_FIXED);
-    if (cost < best_cost) { best_cost = cost; best = mt; }
+  for (int m = 4; m >= 1; --m) {   // ties go to the larger tile (fewer weight re-reads)
+    const int wgs = R * ((T + 16 * m - 1) / (16 * m));
+    const int64_t cost = (int64_t)((wgs + cus - 1) / cus) * (m + MT_FIXED);
+    if (cost < best_cost) { best_cost = cost; best = m; }
   }
   return best;
 }
+// runtime rows-per-tile choice -> template argument: f(std::integral_constant<int, MT>{})
+template <typename F>
+auto with_mt(int mt, F&& f) {
+  switch (mt) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    default: return f(std::integral_constant<int, 4>{});
+  }
+}
 template <int DT>
 void dispatch_head(const cv_tblock_params& p, hipStream_t st) {
-  if constexpr (DT == CV_F16) {   // timing-only ablation builds (wrong results): CV_TBLOCK_ABL=1|2|3
-    static const int abl = env_int("CV_TBLOCK_ABL", 0);
-    if (abl == 1) return launch_head<DT, 4, 1>(p, st);
-    if (abl == 2) return launch_head<DT, 4, 2>(p, st);
-    if (abl == 3) return launch_head<DT, 4, 3>(p, st);
-  }
-  switch (pick_mt(p)) {
-    case 1: return launch_head<DT, 1, 0>(p, st);
-    case 2: return launch_head<DT, 2, 0>(p, st);
-    case 3: return launch_head<DT, 3, 0>(p, st);
-    default: return launch_head<DT, 4, 0>(p, st);
-  }
+  with_mt(pick_mt(p.R, p.T, p.cus, p.mt), [&](auto mt) { launch_head<DT, mt(), 0>(p, st); });
 }
 template <int DT>
 void dispatch_tail_head(const cv_tblock_params& p, hipStream_t st) {
-  switch (pick_mt(p)) {
-    case 1: return launch_tail<DT, true, 1, 0, true>(p, st);
-    case 2: return launch_tail<DT, true, 2, 0, true>(p, st);
-    case 3: return launch_tail<DT, true, 3, 0, true>(p, st);
-    default: return launch_tail<DT, true, 4, 0, true>(p, st);
-  }
+  with_mt(pick_mt(p.R, p.T, p.cus, p.mt), [&](auto mt) { launch_tail<DT, true, mt(), 0, true>(p, st); });
 }
 template <int DT, bool OP>
 void dispatch_tail(const cv_tblock_params& p, hipStream_t st) {
-  if constexpr (DT == CV_F16 && OP) {
-    static const int abl = env_int("CV_TBLOCK_ABL", 0);
-    if (abl == 1) return launch_tail<DT, OP, 4, 1>(p, st);
-    if (abl == 2) return launch_tail<DT, OP, 4, 2>(p, st);
-    if (abl == 3) return launch_tail<DT, OP, 4, 3>(p, st);
-  }
-  switch (pick_mt(p)) {
-    case 1: return launch_tail<DT, OP, 1, 0>(p, st);
-    case 2: return launch_tail<DT, OP, 2, 0>(p, st);
-    case 3: return launch_tail<DT, OP, 3, 0>(p, st);
-    default: return launch_tail<DT, OP, 4, 0>(p, st);
-  }
+  with_mt(pick_mt(p.R, p.T, p.cus, p.mt), [&](auto mt) { launch_tail<DT, OP, mt(), 0>(p, st); });
 }
 
 }  // namespace
@@ -1001,28 +981,15 @@ int launch_resblock(const cv_resblock_params& p, hipStream_t st) {
 }
 template <int STAGE>
 int dispatch_resblock(const cv_resblock_params& p, hipStream_t st) {
-  cv_tblock_params q{};   // tile-size choice shared with the transformer-block kernels
-  q.R = p.R; q.T = p.T; q.cus = p.cus;
-  const int mt = pick_mt(q);
-  if (p.dtype == CV_BF16) {
-    switch (mt) {
-      case 1: return launch_resblock<CV_BF16, STAGE, 1>(p, st);
-      case 2: return launch_resblock<CV_BF16, STAGE, 2>(p, st);
-      case 3: return launch_resblock<CV_BF16, STAGE, 3>(p, st);
-      default: return launch_resblock<CV_BF16, STAGE, 4>(p, st);
-    }
-  }
-  switch (mt) {
-    case 1: return launch_resblock<CV_F16, STAGE, 1>(p, st);
-    case 2: return launch_resblock<CV_F16, STAGE, 2>(p, st);
-    case 3: return launch_resblock<CV_F16, STAGE, 3>(p, st);
-    default: return launch_resblock<CV_F16, STAGE, 4>(p, st);
-  }
+  // tile-size choice shared with the transformer-block kernels
+  return with_mt(pick_mt(p.R, p.T, p.cus, p.mt), [&](auto mt) {
+    return p.dtype == CV_BF16 ? launch_resblock<CV_BF16, STAGE, mt()>(p, st) : launch_resblock<CV_F16, STAGE, mt()>(p, st);
+  });
 }
 int check_resblock(const cv_resblock_params& p, int stage) {
   if (p.dtype != CV_BF16 && p.dtype != CV_F16) return CV_ERR_UNSUPPORTED;
   if (p.C != TB_C || (p.cin != 256 && p.cin != 320 && p.cin != 512)) return CV_ERR_UNSUPPORTED;
-  if (p.R <= 0 || p.T <= 0 || !p.a || (p.lda & 7) || p.lda < p.cin || ((uintptr_t)p.a & 15) || !p.h1 || (p.ldh1 & 7) || ((uintptr_t)p.h1 & 15)) return CV_ERR_ARG;
+  if (p.R <= 0 || p.T <= 0 || !p.a || (p.lda & 7) || p.lda < p.cin || ((uintptr_t)p.a & 15) || !p.h1 || (p.ldh1 & 7) || ((uintptr_t)p.h1 & 15) || p.mt < 0 || p.mt > 4) return CV_ERR_ARG;
   if (stage == 1 && (!p.w1_p || !p.b1 || !p.g1 || !p.be1 || ((uintptr_t)p.w1_p & 15))) return CV_ERR_ARG;
   if (stage == 2 && (!p.w2_p || !p.b2 || !p.g2 || !p.be2 || !p.wr_p || !p.br || !p.out || (p.ldo & 3) || ((uintptr_t)p.out & 15) ||
                      ((uintptr_t)p.w2_p & 15) || ((uintptr_t)p.wr_p & 15))) return CV_ERR_ARG;

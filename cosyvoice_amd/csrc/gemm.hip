@@ -11,7 +11,6 @@
 // One LDS stage + register prefetch: the next tile's global loads fly during the MFMAs; 32 KiB of LDS per 128x128
 // workgroup keeps 4 workgroups resident per CU.
 #include "cv_device.h"
-#include <cstdlib>
 #include <type_traits>
 
 namespace {
@@ -473,160 +472,8 @@ int launch(const cv_gemm_params& p, hipStream_t st) {
   return CV_OK;
 }
 
-// ================================================================================================================
-// gemm_ring_kernel: 128x128 tile, LDS-DMA (global_load_lds, 16 B per lane) into a STAGES-deep ring of 32 KiB stages,
-// counted vmcnt + raw s_barrier so STAGES-1 tiles stay in flight across the MFMA block.  Motivation (measured,
-// DESIGN.md §6): a CU pulls only ~10 B/clk through global loads, so the 64x64 / register-staged kernel is bound by
-// operand traffic (262 MB for a 16000x1024x256 GEMM); a 128x128 tile halves the bytes per flop and the ring keeps the
-// loads in flight at one workgroup per CU.  Same LDS fragment image and epilogue as gemm_kernel.
-// Out-of-range chunks (M/N/K tails, conv padding rows) are fetched from a 16-byte zero word instead of being masked.
+// Out-of-range chunks of an LDS-DMA load (conv padding rows, tails) are fetched from a 16-byte zero word instead of being masked.
 __device__ uint4 g_zero16;
-
-template <int DT, int STAGES>
-__global__ __launch_bounds__(256) void gemm_ring_kernel(const cv_gemm_params p) {
-  constexpr int BM = 128, BN = 128, MT = 4, NT = 4;
-  constexpr int ES = ElemSize<DT>::value;
-  constexpr int CH = 16 / ES;
-  constexpr int BK = 128 / ES;
-  constexpr int STAGE = (BM + BN) * 128;
-  constexpr int NB = 8;  // 1 KiB blocks (16 rows x 4 chunks) per wave per tile: waves 0,1 load A, waves 2,3 load W
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  typedef __attribute__((address_space(3))) void* lds_ptr_t;
-  typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wave_m = wid >> 1, wave_n = wid & 1;
-  // byte offset of this lane's fragment chunk inside a 16-row (2 KiB) block, for k half 0 / 1
-  const int frag_off[2] = {((lane & 15) << 7) + ((((lane >> 4)) ^ (((lane & 15) >> 1) & 7)) << 4),
-                           ((lane & 15) << 7) + (((4 + (lane >> 4)) ^ (((lane & 15) >> 1) & 7)) << 4)};
-  const int mtiles = (p.M + BM - 1) / BM, ntiles = (p.N + BN - 1) / BN;
-  int tile_m, tile_n;
-  {
-    const int nwg = gridDim.x, orig = blockIdx.x;
-    const int xcd = orig & 7, q = nwg >> 3, r = nwg & 7;
-    const int id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
-    if (p.N <= p.M) { tile_n = id % ntiles; tile_m = id / ntiles; }
-    else { tile_m = id % mtiles; tile_n = id / mtiles; }
-  }
-  const int m0 = tile_m * BM, n0 = tile_n * BN;
-  const int z = blockIdx.z;
-  const int z1 = z / p.batch_inner, z0 = z - z1 * p.batch_inner;
-  int a_len = p.a_rows;   // ragged batches: as in gemm_kernel
-  if (p.len_base) {
-    const int base = __builtin_amdgcn_readfirstlane(p.len_base[z]);
-    if ((p.m_len_mul | p.m_len_add) && m0 >= base * p.m_len_mul + p.m_len_add) return;
-    if (p.a_len_mul | p.a_len_add) a_len = min(a_len, base * p.a_len_mul + p.a_len_add);
-  }
-  const char* Ab = (const char*)p.A + (z0 * p.a_bs0 + z1 * p.a_bs1) * ES;
-  const char* Wb = (const char*)p.W + (z0 * p.w_bs0 + z1 * p.w_bs1) * ES;
-  const int nk = (p.K + BK - 1) / BK;
-  const bool conv = p.cin != p.K;
-  const bool load_a = wid < 2;
-  const char* zero = (const char*)&g_zero16;
-
-  // LDS-DMA writes 1 KiB per wave instruction at base + lane*16 = 8 consecutive rows x 8 chunk slots of the row-major
-  // image; the XOR swizzle therefore goes on the SOURCE: lane (row lr8 = lane>>3, slot = lane&7) fetches chunk
-  // slot ^ ((row>>1)&7) of its row (cdna guide rule 21: linear dest + swizzled source + swizzled read).
-  // block j (of 8) of this wave covers rows (wid&1)*64 + j*8 .. +7 of the A (waves 0,1) or W (waves 2,3) tile.
-  const int lr8 = lane >> 3, slot = lane & 7;
-  int rowbase[NB];
-  bool rok[NB];
-  const char* rptr[NB];  // non-conv A / W: pointer to (row, chunk) at k = 0
-  int kch[NB];           // source chunk index (0..7) of this lane in block j
-#pragma unroll
-  for (int j = 0; j < NB; ++j) {
-    const int row = (wid & 1) * 64 + j * 8 + lr8;
-    kch[j] = slot ^ ((row >> 1) & 7);
-    if (load_a) {
-      const int m = m0 + row;
-      rowbase[j] = m * p.a_row_stride + p.tap_base;
-      rok[j] = m < p.M;
-      const int arow = rowbase[j];
-      if (!conv) rok[j] = rok[j] && arow >= 0 && arow < a_len;
-      rptr[j] = Ab + ((int64_t)min(max(arow, 0), p.a_rows - 1) * p.lda + kch[j] * CH) * ES;
-    } else {
-      const int n = n0 + row;
-      rowbase[j] = 0;
-      rok[j] = n < p.N;
-      rptr[j] = Wb + ((int64_t)min(n, p.N - 1) * p.ldw + kch[j] * CH) * ES;
-    }
-  }
-
-  auto issue = [&](int kt, int stage) {
-    char* sbase = smem + stage * STAGE + (load_a ? 0 : BM * 128) + (wid & 1) * (NB * 1024);
-    const int kbase = kt * BK;
-#pragma unroll
-    for (int j = 0; j < NB; ++j) {
-      const int k = kbase + kch[j] * CH;
-      const char* src;
-      if (load_a && conv) {
-        const int tap = k / p.cin, ci = k - tap * p.cin;
-        const int arow = rowbase[j] + tap * p.tap_step;
-        const bool ok = rok[j] && k < p.K && arow >= 0 && arow < a_len;
-        src = ok ? Ab + ((int64_t)arow * p.lda + ci) * ES : zero;
-      } else {
-        const bool ok = rok[j] && k < p.K;
-        src = ok ? rptr[j] + (int64_t)kbase * ES : zero;
-      }
-      __builtin_amdgcn_global_load_lds((gbl_ptr_t)src, (lds_ptr_t)(sbase + j * 1024), 16, 0, 0);
-    }
-  };
-
-  f32x4_t acc[MT][NT];
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int j = 0; j < NT; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-
-  // prologue: STAGES-1 tiles in flight
-#pragma unroll
-  for (int s2 = 0; s2 < STAGES - 1; ++s2)
-    if (s2 < nk) issue(s2, s2);
-
-  for (int kt = 0; kt < nk; ++kt) {
-    const int stage = kt % STAGES;
-    if (kt + STAGES - 1 < nk) issue(kt + STAGES - 1, (kt + STAGES - 1) % STAGES);
-    // tiles still allowed in flight after this wait: min(STAGES-1, nk-1-kt), 8 loads each
-    const int ahead = min(STAGES - 1, nk - 1 - kt);
-    if (ahead >= 3) asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
-    else if (ahead == 2) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-    else if (ahead == 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    const char* sa = smem + stage * STAGE;
-    const char* sb = sa + BM * 128;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      uint4 fa[MT], fb[NT];
-#pragma unroll
-      for (int i = 0; i < MT; ++i) fa[i] = *(const uint4*)(sa + ((wave_m * MT + i) << 11) + frag_off[ks]);
-#pragma unroll
-      for (int j = 0; j < NT; ++j) fb[j] = *(const uint4*)(sb + ((wave_n * NT + j) << 11) + frag_off[ks]);
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j) acc[i][j] = mfma_block<DT>(fb[j], fa[i], acc[i][j]);
-    }
-    // WAR: this stage is refilled by the issue() of the next iteration
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-  }
-  gemm_epilogue<DT, MT, NT>(p, acc, m0, n0, wave_m, wave_n, lane, z, z0, z1);
-}
-
-template <int DT>
-int launch_ring(const cv_gemm_params& p, hipStream_t st) {
-  const int mt = (p.M + 127) / 128, nt = (p.N + 127) / 128;
-  dim3 grid(mt * nt, 1, p.batch);
-  constexpr int STAGES = 3;
-  const size_t lds = (size_t)STAGES * 256 * 128;
-  static PerDeviceOnce once;
-  once.run([&] { hipFuncSetAttribute((const void*)gemm_ring_kernel<DT, STAGES>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); });
-  hipLaunchKernelGGL((gemm_ring_kernel<DT, STAGES>), grid, dim3(256), lds, st, p);
-  CV_CHECK_LAUNCH();
-  return CV_OK;
-}
 
 // ================================================================================================================
 // conv_win_kernel: stride-1 Conv1d on the bf16x3 path with both operands pre-split (the HiFT / BigVGAN ResBlock convs: 91 % of the
@@ -748,8 +595,8 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv_win_kernel(const cv_gemm
   gemm_epilogue<CV_F32, MT, NT, true>(p, acc, m0, n0, wave_m, wave_n, lane, z, z0, z1);
 }
 
-// CV_CONV_WIN=1 opts the qualifying convs in (default: gemm_kernel); CV_CONV_WIN_SHAPE=WMxWN forces one workgroup shape.  Both are read per
-// call.  Measured (tools/hift_conv_bench.py, profiles/r03_hift_conv_bench.log, DESIGN.md status item 4): alone, on the c1-type launch (snake +
+// p.conv_win = 1 opts the qualifying convs in (0, the default: gemm_kernel); 10 WM + WN forces one workgroup shape.
+// Measured (tools/hift_conv_bench.py, profiles/r03_hift_conv_bench.log, DESIGN.md status item 4): alone, on the c1-type launch (snake +
 // pre-split output), the window kernel is 5 - 20 % faster on every batch-8 shape (1 282 vs 1 501 us over the nine shapes) and within +-10 % on
 // single-utterance grids; inside a decode, where every second conv also reads the residual and writes the fp32 stream, the advantage shrinks to 3 %
 // at batch 8 (12.3 vs 12.65 ms of conv time) and turns into a 4 % loss at batch 1 (3.67 vs 3.51 ms per decode) — its window load, taps and
@@ -772,16 +619,15 @@ int launch_conv_win(const cv_gemm_params& p, hipStream_t st, int halo) {
 // returns CONV_WIN_NO when the launch does not qualify (the caller falls through to gemm_kernel)
 constexpr int CONV_WIN_NO = 1;
 int dispatch_conv_win(const cv_gemm_params& p, hipStream_t st) {
-  int force_wm = 0, force_wn = 0;
-  if (const char* e = getenv("CV_CONV_WIN"); !e || atoi(e) != 1) return CONV_WIN_NO;
+  if (!p.conv_win) return CONV_WIN_NO;
   if (p.len_base) return CONV_WIN_NO;   // ragged batches: the window loader knows one a_rows for the whole launch
-  if (const char* s = getenv("CV_CONV_WIN_SHAPE"); s && s[0] >= '1' && s[0] <= '4' && s[1] == 'x' && s[2] >= '1' && s[2] <= '2') { force_wm = s[0] - '0'; force_wn = s[2] - '0'; }
+  const int force_wm = p.conv_win / 10, force_wn = p.conv_win % 10;   // 0, 1 for the automatic shape (cv_gemm has checked the value)
   if (p.cin == p.K || (p.x3_flags & 3) != 3 || p.a_row_stride != 1 || p.tap_step <= 0) return CONV_WIN_NO;
   if ((p.cin & 63) || (p.N & 63) || p.act == CV_ACT_SWIGLU || p.out_mode != CV_OUT_ROWMAJOR) return CONV_WIN_NO;
   if ((int64_t)p.N * p.ldw * 4 > 0x7FFFFFFF) return CONV_WIN_NO;
   const int halo = (p.K / p.cin - 1) * p.tap_step;
   int wm, wn = (p.N >= 128) ? 2 : 1;
-  if (force_wm) { wm = force_wm == 3 ? 2 : force_wm; wn = min(force_wn, wn); }
+  if (force_wm) { wm = force_wm; wn = min(force_wn, wn); }
   else {
     // waves per workgroup by the number of 64 x 64 wave tiles in the launch (tools/hift_conv_bench.py: one-wave workgroups win on single-utterance
     // grids of 250 - 940 tiles, two waves at 2 000, four from 5 000); four waves = 128 x 128 where N allows, else 256 x 64
@@ -800,9 +646,6 @@ int dispatch_conv_win(const cv_gemm_params& p, hipStream_t st) {
   return CONV_WIN_NO;
 }
 
-// CV_GEMM_TILE=0|1|2|3 (128x128 | 128x64 | 64x64 | 128x128 LDS-DMA ring) overrides the heuristic: tuning aid only
-static int g_tile_override = -2;
-
 // fp32 tensors, bf16x3 products: the two register-staged tiles only
 int dispatch_x3(const cv_gemm_params& p, hipStream_t st) {
   if (const int rc = dispatch_conv_win(p, st); rc != CONV_WIN_NO) return rc;
@@ -819,29 +662,16 @@ int dispatch_x3(const cv_gemm_params& p, hipStream_t st) {
 
 template <int DT>
 int dispatch(const cv_gemm_params& p, hipStream_t st) {
-  if (g_tile_override == -2) {
-    const char* e = getenv("CV_GEMM_TILE");
-    g_tile_override = e ? atoi(e) : -1;
-  }
-  const bool swiglu = p.act == CV_ACT_SWIGLU;
-  int tile = g_tile_override;
-  if (tile < 0) {
-    // These GEMMs have short K (256..1024): latency is hidden by resident workgroups, not by pipeline depth, so prefer
-    // the largest tile that still puts >= ~4 workgroups on every CU.
-    // measured on MI355X (tools/gemm_bench.py, profiles/r01_gemm_tile_sweep.txt): 64x64 wins for K <= 512 and whenever
-    // 128x64 would leave < ~3 workgroups per CU; 128x64 wins for long K with many tiles; 128x128 never wins here.
-    const long long t12864 = (long long)((p.M + 127) / 128) * ((p.N + 63) / 64) * p.batch;
-    if (p.K > 512 && t12864 >= 768) tile = 1;
-    else tile = 2;
-    // very tall GEMMs with wide N and K (the LLM prefill of a 4-batch decode job: 9 024 rows): the 8-wave 128 x 128 tile halves the
-    // operand bytes per flop (tools/prefill_probe.py: 18.8 -> 16.2 ms at 32 sequences; slower at 8 sequences = 2 256 rows)
-    if (p.batch == 1 && p.M >= 8192 && p.N >= 512 && p.K >= 512) tile = 4;
-  }
-  if (swiglu && (tile == 0 || tile == 3)) tile = 1;
-  if (tile == 3) return launch_ring<DT>(p, st);
-  if (tile == 4) return launch<DT, 128, 128, 2, 4>(p, st);  // 8 waves, wave tile 64x32
-  if (tile == 0) return launch<DT, 128, 128>(p, st);
-  if (tile == 1) return launch<DT, 128, 64>(p, st);
+  // These GEMMs have short K (256..1024): latency is hidden by resident workgroups, not by pipeline depth, so prefer
+  // the largest tile that still puts >= ~4 workgroups on every CU.
+  // measured on MI355X (tools/gemm_bench.py, profiles/r01_gemm_tile_sweep.txt): 64x64 wins for K <= 512 and whenever
+  // 128x64 would leave < ~3 workgroups per CU; 128x64 wins for long K with many tiles; the 4-wave 128x128 tile and its
+  // LDS-DMA ring form never won here and are gone (DESIGN.md §6 "larger tiles").
+  // very tall GEMMs with wide N and K (the LLM prefill of a 4-batch decode job: 9 024 rows): the 8-wave 128 x 128 tile halves the
+  // operand bytes per flop (tools/prefill_probe.py: 18.8 -> 16.2 ms at 32 sequences; slower at 8 sequences = 2 256 rows)
+  if (p.batch == 1 && p.M >= 8192 && p.N >= 512 && p.K >= 512) return launch<DT, 128, 128, 2, 4>(p, st);  // wave tile 64x32
+  const long long t12864 = (long long)((p.M + 127) / 128) * ((p.N + 63) / 64) * p.batch;
+  if (p.K > 512 && t12864 >= 768) return launch<DT, 128, 64>(p, st);
   return launch<DT, 64, 64>(p, st);
 }
 
@@ -881,6 +711,7 @@ extern "C" int cv_gemm(const cv_gemm_params* pp, void* stream) {
     if (p.out_act && ((p.ldoa & 3) || ((uintptr_t)p.out_act & 15) || (p.oa_bs0 & 3) || (p.oa_bs1 & 3))) return CV_ERR_ARG;
   }
   if (p.x3_flags && (!x3 || (p.x3_flags & ~7))) return CV_ERR_ARG;          // pre-split storage belongs to CV_F32X3 launches
+  if (const int w = p.conv_win; w != 0 && w != 1 && w != 41 && w != 22 && w != 21 && w != 12 && w != 11) return CV_ERR_ARG;
   if ((p.x3_flags & 4) && (!p.out_act || (p.N & 7) || (p.ldoa & 7) || p.act == CV_ACT_SWIGLU || p.out_mode != CV_OUT_ROWMAJOR)) return CV_ERR_ARG;
   if ((p.x3_flags & 3) && ((p.K & 7) || (p.cin & 7) || (p.lda & 7) || (p.ldw & 7))) return CV_ERR_ARG;   // 8-value groups
   if (!p.len_base) {   // ragged-batch fields without the length array

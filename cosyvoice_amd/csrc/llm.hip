@@ -679,7 +679,7 @@ constexpr int DA_WAVES = 8;
 // and loaded a wave's second tile only after finishing its first: two more dependent HBM round trips, 8.5 us per call.)
 // FUSED is a template parameter, not `qkv != nullptr` at run time: a run-time branch around the qkv loads ends in PHIs
 // with the zero defaults, and hipcc then waits for those loads before it issues the K/V tile loads.
-template <int DT, bool FUSED, int ABL = 0>   // ABL: timing-only ablations (CV_DA_ABL; results are wrong): 1 no MFMA/softmax, 2 no K/V loads
+template <int DT, bool FUSED, int ABL = 0>   // ABL: timing-only ablations (results are wrong; instantiated by hand for a measurement, DESIGN.md §4 decode_attn_kernel row): 1 no MFMA/softmax, 2 no K/V loads
 __global__ __launch_bounds__(512) void decode_attn_kernel(const uint16_t* q, int ldq, uint16_t* kcache, uint16_t* vtcache,
                                                           const int32_t* ctx_len, int ctx_add, uint16_t* out, int ldo, int Hq, int Hkv,
                                                           int ctx_max, float scale, const float* qkv, int ldqkv, const float* inv_freq) {
@@ -1491,16 +1491,7 @@ extern "C" int cv_decode_attention(const void* q, int32_t ldq, const void* kcach
   if (qkv && (!inv_freq || ldqkv < (Hq + 2 * Hkv) * 64)) return CV_ERR_ARG;
   if ((ldo & 3) || (ctx_max & 63)) return CV_ERR_ARG;
   dim3 grid(Hkv, B);
-  static const int abl = getenv("CV_DA_ABL") ? atoi(getenv("CV_DA_ABL")) : 0;
-  if (qkv && abl == 1) {
-    DISPATCH_16(dtype, hipLaunchKernelGGL((decode_attn_kernel<DT, true, 1>), grid, dim3(512), 0, (hipStream_t)stream, (const uint16_t*)q, ldq,
-                                          (uint16_t*)kcache, (uint16_t*)vtcache, ctx_len, ctx_add, (uint16_t*)out, ldo, Hq, Hkv,
-                                          ctx_max, scale, qkv, ldqkv, inv_freq));
-  } else if (qkv && abl == 2) {
-    DISPATCH_16(dtype, hipLaunchKernelGGL((decode_attn_kernel<DT, true, 2>), grid, dim3(512), 0, (hipStream_t)stream, (const uint16_t*)q, ldq,
-                                          (uint16_t*)kcache, (uint16_t*)vtcache, ctx_len, ctx_add, (uint16_t*)out, ldo, Hq, Hkv,
-                                          ctx_max, scale, qkv, ldqkv, inv_freq));
-  } else if (qkv) {
+  if (qkv) {
     DISPATCH_16(dtype, hipLaunchKernelGGL((decode_attn_kernel<DT, true>), grid, dim3(512), 0, (hipStream_t)stream, (const uint16_t*)q, ldq,
                                           (uint16_t*)kcache, (uint16_t*)vtcache, ctx_len, ctx_add, (uint16_t*)out, ldo, Hq, Hkv,
                                           ctx_max, scale, qkv, ldqkv, inv_freq));

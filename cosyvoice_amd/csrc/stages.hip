@@ -290,6 +290,7 @@ int hconv(const cv_hift_decode_desc& d, const cv_hift_conv& c, const void* x, in
   if (e.out_act) { p.out_act = e.out_act; p.oa_bs0 = (int64_t)T_out * c.cout; p.ldoa = c.cout; }
   p.out_row_stride = 1;
   p.x3_flags = e.out_act ? c.x3_flags : (c.x3_flags & ~4);
+  p.conv_win = c.conv_win;
   if (d.lens) { p.len_base = d.lens; p.a_len_mul = in.mul; p.a_len_add = in.add; p.m_len_mul = out.mul; p.m_len_add = out.add; }
   return cv_gemm(&p, st);
 }

@@ -74,13 +74,16 @@ class _ConvT:
 
 class HiFTGenerator:
     def __init__(self, cfg: Optional[HiftConfig] = None, dtype: torch.dtype = torch.float32, device: str = "cuda",
-                 f32_products: str = "bf16x3"):
+                 f32_products: str = "bf16x3", conv_win: int = 0):
         self.cfg = cfg or HiftConfig.v2()
         self.dtype = dtype
         # fp32 operands (the reference never halves HiFT): "exact" = f32 MFMA; "bf16x3" = three bf16 MFMAs on hi/lo splits per
         # product (~2^-16 relative, ~3x faster) for the decoder convs.  The F0 predictor always runs exact: its output feeds a
         # phase accumulation over 240 000 samples.
         self.f32_products = f32_products
+        # cv_gemm_params.conv_win of every conv launch (0 = the implicit-GEMM kernel, 1 = the activation-window kernel where a conv
+        # qualifies, 10 WM + WN = that kernel in one workgroup shape).  Fixed here: workspaces and descriptors are cached per shape.
+        self.conv_win = conv_win
         self.device = torch.device(device)
         self.num_kernels = len(self.cfg.resblock_kernel_sizes)
         self.num_upsamples = len(self.cfg.upsample_rates)
@@ -209,7 +212,8 @@ class HiFTGenerator:
         w = c.w_s.view(torch.float32) if (flags & 2) else c.w
         if kw.get("out_act") is None:
             flags &= ~4
-        ops.conv1d_cl(x, w, c.k, dilation=c.dilation, pad_left=c.pad_left, stride=c.stride, T_out=T_out, bias=c.b, x3_flags=flags, **kw)
+        ops.conv1d_cl(x, w, c.k, dilation=c.dilation, pad_left=c.pad_left, stride=c.stride, T_out=T_out, bias=c.b, x3_flags=flags,
+                      conv_win=self.conv_win, **kw)
 
     def _resblock(self, rb, x32, xa, ws, i, final):
         """x32: fp32 block input; xa: snake_{a1[0]}(x32) in dtype.  ``final`` = kwargs of the last conv2's epilogue
@@ -305,7 +309,7 @@ class HiFTGenerator:
             h = L.HiftConv()
             h.w, h.b = (c.w_s if (flags & 2) else c.w).data_ptr(), (c.b.data_ptr() if c.b is not None else None)
             h.k, h.cin, h.cout, h.dilation, h.pad_left, h.stride = c.k, cin, c.cout, c.dilation, c.pad_left, c.stride
-            h.x3_flags = flags
+            h.x3_flags, h.conv_win = flags, self.conv_win
             return h
 
         def resblock(rb, ch):

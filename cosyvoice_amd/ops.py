@@ -110,8 +110,9 @@ def gemm(A, W, M, N, K, *, dtype=None, batch=1, batch_inner=0, a_bs=(0, 0), lda=
          a_row_stride=1, tap_base=0, tap_step=0, w_bs=(0, 0), ldw=None, bias=None, res=None, res_bs=(0, 0), ldres=0,
          res2=None, ldres2=0, out_scale=1.0, act=ACT_NONE, act_param=None, act_slope=0.0, out_f32=None, o32_bs=(0, 0),
          ldo32=0, out_act=None, oa_bs=(0, 0), ldoa=0, out_row_stride=1, out_row_off=0, out_rows=0, qkv=None, x3_flags=0,
-         lens=None, a_len=(0, 0), m_len=(0, 0)):
-    """``lens`` (device int32 (batch,), off by default) makes the launch ragged (cv_gemm_params.len_base): batch z reads zeros past its
+         lens=None, a_len=(0, 0), m_len=(0, 0), conv_win=0):
+    """``conv_win``: cv_gemm_params.conv_win (0 the library's choice, 1 the window kernel, 10 WM + WN that kernel in one workgroup shape).
+    ``lens`` (device int32 (batch,), off by default) makes the launch ragged (cv_gemm_params.len_base): batch z reads zeros past its
     own ``lens[z] * a_len[0] + a_len[1]`` rows of A and only its first ``lens[z] * m_len[0] + m_len[1]`` output rows are needed."""
     _req_cuda(A, W, bias, res, res2, out_f32, out_act, lens)
     p = L.GemmParams()
@@ -130,6 +131,7 @@ def gemm(A, W, M, N, K, *, dtype=None, batch=1, batch_inner=0, a_bs=(0, 0), lda=
     p.out_act, p.oa_bs0, p.oa_bs1, p.ldoa = L.ptr(out_act), oa_bs[0], oa_bs[1], ldoa
     p.out_row_stride, p.out_row_off, p.out_rows = out_row_stride, out_row_off, out_rows
     p.x3_flags = x3_flags if p.dtype == L.CV_F32X3 else 0   # pre-split operand / output storage of the bf16x3 path (cv_gemm_params.x3_flags)
+    p.conv_win = conv_win
     if lens is not None:
         assert lens.dtype == torch.int32 and lens.is_contiguous() and lens.numel() >= batch
         p.len_base = lens.data_ptr()
@@ -187,7 +189,8 @@ def layernorm(x, gamma, beta, eps, *, rms=False, add=None, rows_per_group=0, act
 
 
 def attention(q, k, vt, out, *, H, Hkv, Tq, Tk, scale, q_bs, ldq, k_bs, ldk, vt_ld, o_bs, ldo, B, klen=None, chunk=0,
-              causal=False, causal_off=0, bias=None, bias_bs=0, bias_hs=0, bias_ld=0, q_hs=0, k_hs=0, q_off=0):
+              causal=False, causal_off=0, bias=None, bias_bs=0, bias_hs=0, bias_ld=0, q_hs=0, k_hs=0, q_off=0, mfma=0, waves=0):
+    """``mfma`` / ``waves``: kernel variant fields of cv_attn_params (0 = the library's choice)."""
     _req_cuda(q, k, vt, out, klen, bias)
     p = L.AttnParams()
     p.dtype = L.TORCH_DT[q.dtype]
@@ -199,6 +202,7 @@ def attention(q, k, vt, out, *, H, Hkv, Tq, Tk, scale, q_bs, ldq, k_bs, ldk, vt_
     p.scale, p.klen, p.chunk, p.causal, p.causal_off = scale, L.ptr(klen), chunk, int(causal), causal_off
     p.bias, p.bias_bs, p.bias_hs, p.bias_ld = L.ptr(bias), bias_bs, bias_hs, bias_ld
     p.q_hs, p.k_hs, p.q_off = q_hs, k_hs, q_off
+    p.mfma, p.waves = mfma, waves
     _issue("cv_attention", p)
 
 

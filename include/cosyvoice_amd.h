@@ -31,7 +31,7 @@ typedef enum {
 } cv_act;
 typedef enum { CV_OUT_ROWMAJOR = 0, CV_OUT_QKV = 1 } cv_out_mode;
 
-int cv_version(void);
+int cv_version(void);   /* bumped whenever a struct of this header changes size or layout (2: the variant fields mfma / waves / mt / conv_win) */
 const char* cv_arch(void); /* "gfx950" */
 
 /* ------------------------------------------------------------------------------------------
@@ -72,13 +72,19 @@ typedef struct cv_gemm_params {
    * (row lengths / K / cin / leading dimensions % 8 == 0).
    * bit 0: A is pre-split; bit 1: W is pre-split (both or neither); bit 2: out_act is WRITTEN pre-split (row-major, N % 8 == 0).
    * Results are bit-identical to the plain CV_F32X3 launch. */
-  int32_t x3_flags; int32_t reserved_x3;
+  int32_t x3_flags;
+  /* conv_win — kernel variant for stride-1 convs with both operands pre-split: 0 = the library's choice (the implicit-GEMM kernel);
+   * 1 = the activation-window kernel, workgroup shape chosen by the launch size; 10*WM + WN in {41, 22, 21, 12, 11} = that kernel with
+   * WM x WN waves per workgroup (WN = 2 becomes 1 when N < 128, WM is halved until the window fits in LDS).  A launch that does not
+   * qualify (not a conv, operands not pre-split, cin or N not a multiple of 64, SwiGLU, CV_OUT_QKV, ragged) takes the implicit-GEMM
+   * kernel whatever the field says.  Any other value: CV_ERR_ARG.  Same results up to the fp32 summation order. */
+  int32_t conv_win;
   /* RAGGED batches (all zero / NULL = off, the behaviour above).  len_base: DEVICE int32 [batch], a base length per batch index z (read by the
    * kernel, so a captured graph serves any lengths).  A rows at or past  a_len(z) = min(a_rows, len_base[z]*a_len_mul + a_len_add)  read as
    * zero whatever the buffer holds there (a_len_mul = a_len_add = 0: a_len = a_rows);  only the first  m_len(z) = len_base[z]*m_len_mul +
    * m_len_add  of the M rows are needed: a workgroup whose rows all lie at or past m_len(z) returns without touching memory, rows past
    * m_len(z) inside a live tile may still be stored (m_len_mul = m_len_add = 0: m_len = M).  Addresses are clamped with a_rows / M, never with
-   * the device values.  Needs batch_inner == batch and CV_OUT_ROWMAJOR; not taken by the opt-in window kernel (CV_CONV_WIN). */
+   * the device values.  Needs batch_inner == batch and CV_OUT_ROWMAJOR; not taken by the opt-in window kernel (conv_win). */
   const int32_t* len_base; int32_t a_len_mul, a_len_add, m_len_mul, m_len_add;
 } cv_gemm_params;
 int cv_gemm(const cv_gemm_params* p, void* stream);
@@ -146,6 +152,9 @@ typedef struct cv_attn_params {
   int32_t q_off;            /* chunk mask: query row i sits at position q_off + i of the key sequence (incremental encoder: only the
                                rows behind the cached prefix are queries); 0 = queries and keys start together */
   int64_t q_hs, k_hs;       /* element stride between heads of Q / K (0 -> 64: heads packed inside a row) */
+  /* kernel variants: same results up to the order of the fp32 sums; 0 = the library's choice; any value not listed: CV_ERR_ARG */
+  int32_t mfma;             /* 0 / 16: the 16x16x32-MFMA kernel; 32: the 32x32x16 form; 64: 64 queries per wave (with a bias, or Tk < 8, the 16 form) */
+  int32_t waves;            /* waves per workgroup of the 16 and 32 forms: 0 = 2 when H * ceil(Tq / 128) * B < 256, else 4; or 2, 4 */
 } cv_attn_params;
 int cv_attention(const cv_attn_params* p, void* stream);
 
@@ -182,6 +191,7 @@ typedef struct cv_tblock_params {
   void* out_act; int32_t ldoa;            /* optional 16-bit copy of the block output [R * T][ldoa] */
   int32_t cus;                            /* CUs the launch may use (a CU-masked stream's share); 0 = the whole chip.  Speed only:
                                              picks 48- or 64-row tiles so that the grid does not end in a nearly empty round */
+  int32_t mt;                             /* rows per workgroup = 16 mt: 0 = the library's choice (from R, T, cus), or 1..4; else CV_ERR_ARG */
 } cv_tblock_params;
 int cv_sizeof_tblock_params(void);
 int cv_tblock_head(const cv_tblock_params* p, void* stream);
@@ -210,6 +220,7 @@ typedef struct cv_resblock_params {
   const void* wr_p; const float* br;
   float* out; int32_t ldo;
   float eps; int32_t cus;
+  int32_t mt;                 /* as cv_tblock_params.mt */
 } cv_resblock_params;
 int cv_sizeof_resblock_params(void);
 int cv_resblock_conv1(const cv_resblock_params* p, void* stream);
@@ -554,7 +565,8 @@ int cv_flow_euler_graph_destroy(void* graph);
  * Needs S == T * prod(u) * hop and stages[i].t_out == T * prod(u[0..i]) (+ 1 on the last stage). */
 typedef struct cv_hift_conv {        /* channels-last Conv1d: w [cout][k*cin] with k index = tap*cin + ci; cin = channel pitch of its input */
   const void* w; const float* b; int32_t k, cin, cout, dilation, pad_left, stride;
-  int32_t x3_flags, reserved;        /* gemm_dtype CV_F32X3: cv_gemm_params.x3_flags of this conv (bit 2 is dropped when it has no 16/32-bit activation output) */
+  int32_t x3_flags, conv_win;        /* gemm_dtype CV_F32X3: cv_gemm_params.x3_flags of this conv (bit 2 is dropped when it has no 16/32-bit activation output)
+                                        and cv_gemm_params.conv_win of its launch */
 } cv_hift_conv;
 typedef struct cv_hift_resunit { cv_hift_conv c1, c2; const float* a1; const float* a2; } cv_hift_resunit;   /* Snake alphas [C] */
 typedef struct cv_hift_resblock { const cv_hift_resunit* units; int32_t n_units, reserved; } cv_hift_resblock;

@@ -71,6 +71,56 @@ def test_argument_validation_returns_status_codes_without_a_gpu():
     assert lib.cv_hift_decode_enqueue(None, null) < 0
 
 
+def _variant_blocks():
+    """Parameter blocks that pass every check of their entry point (dummy aligned pointers, never dereferenced: nothing may be launched
+    with them), paired with the entry point and the (variant field, out-of-range value) to set."""
+    from cosyvoice_amd import _lib as L
+    a = L.AttnParams()
+    a.dtype, a.B, a.H, a.Hkv, a.Tq, a.Tk = L.CV_BF16, 1, 1, 1, 16, 16
+    a.q = a.k = a.vt = a.out = 16
+    a.ldq, a.ldk, a.vt_ld, a.ldo, a.scale = 64, 64, 16, 64, 0.125
+    t = L.TBlockParams()
+    t.dtype, t.R, t.T, t.C, t.inner, t.ff = L.CV_BF16, 1, 16, 256, 512, 1024
+    t.x = t.g1 = t.b1n = t.wqkv_p = t.qk = t.vt = 16
+    t.ldx, t.eps, t.ldqk, t.vt_ld = 256, 1e-5, 1024, 16
+    r = L.ResblockParams()
+    r.dtype, r.R, r.T, r.C, r.cin = L.CV_BF16, 1, 16, 256, 256
+    r.a = r.w1_p = r.b1 = r.g1 = r.be1 = r.h1 = 16
+    r.lda, r.ldh1, r.eps = 256, 256, 1e-5
+    g = L.GemmParams()                 # a k = 3 conv on pre-split operands, pre-split activation output
+    g.dtype, g.M, g.N, g.K, g.batch, g.cin, g.tap_step, g.x3_flags = L.CV_F32X3, 64, 64, 192, 1, 64, 1, 7
+    g.A = g.W = g.out_f32 = g.out_act = 16
+    g.lda, g.ldw, g.ldo32, g.ldoa = 64, 192, 64, 64
+    return [("cv_attention", a, "mfma", 48), ("cv_attention", a, "waves", 3), ("cv_tblock_head", t, "mt", 5),
+            ("cv_resblock_conv1", r, "mt", 5), ("cv_gemm", g, "conv_win", 33)]
+
+
+def test_out_of_range_variant_fields_are_rejected_without_a_gpu():
+    """The kernel-variant fields (cv_attn_params.mfma / waves, cv_tblock_params.mt, cv_resblock_params.mt, cv_gemm_params.conv_win)
+    select among tested kernels; a value outside the documented set is CV_ERR_ARG before anything is launched, never silently the
+    library's own choice."""
+    from cosyvoice_amd import _lib as L
+    lib = L.lib()
+    null = ctypes.c_void_p(None)
+    CV_ERR_ARG = -1
+    for entry, p, field, bad in _variant_blocks():
+        assert getattr(p, field) == 0
+        setattr(p, field, bad)
+        assert getattr(lib, entry)(ctypes.byref(p), null) == CV_ERR_ARG, (entry, field, bad)
+        setattr(p, field, -1)
+        assert getattr(lib, entry)(ctypes.byref(p), null) == CV_ERR_ARG, (entry, field, -1)
+        setattr(p, field, 0)
+
+
+def test_csrc_reads_no_environment_variable():
+    """Kernel variants are chosen by fields of a call's own parameter block: no source of the library calls getenv."""
+    csrc = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "cosyvoice_amd", "csrc")
+    files = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".h")))
+    assert len(files) >= 10, files
+    for f in files:
+        assert "getenv" not in open(os.path.join(csrc, f)).read(), f
+
+
 def test_version_and_unbound_entry_points_reject_null_arguments():
     """cv_version, and the entry points no Python wrapper calls (aliases of cv_graph_launch / cv_graph_destroy / cv_hift_decode_enqueue, and
     the *_enqueue forms of the composed stages): they answer, and reject null descriptors / handles with a status code."""

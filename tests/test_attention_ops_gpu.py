@@ -25,8 +25,8 @@ Nothing here is fitted to the kernels.  ``test_cpu_attention_bound`` (no gpu mar
 (H.attn_emulate) on every GPU case: it meets the bound, and it misses it as soon as one mask is widened by one key, so the cases have teeth
 and a miss on the device belongs to the kernel.
 
-Dispatch (cv_attention): CV_ATTN_MFMA 16 -> attn_kernel, 32 -> attn32_kernel, 64 -> attn64_kernel, which takes no bias: with a bias the
-dispatcher falls through to the 16 form; CV_ATTN_WAVES 2 / 4 the workgroup shape of the 16 and 32 forms.  Every case runs all six."""
+Dispatch (cv_attention): cv_attn_params.mfma 16 -> attn_kernel, 32 -> attn32_kernel, 64 -> attn64_kernel, which takes no bias: with a bias the
+dispatcher falls through to the 16 form; cv_attn_params.waves 2 / 4 the workgroup shape of the 16 and 32 forms.  Every case runs all six."""
 import functools
 import os
 import sys
@@ -168,8 +168,8 @@ def _r(x, m):
     return (x + m - 1) // m * m
 
 
-def _launch(c, dt, q, k, v, bias, ok):
-    """Builds the poisoned / guarded device buffers of the case's layout, runs ops.attention and returns (out (B, H, Tq, 64) on the CPU, the
+def _launch(c, dt, q, k, v, bias, ok, mfma, waves):
+    """Builds the poisoned / guarded device buffers of the case's layout, runs ops.attention (kernel variant ``mfma`` / ``waves``) and returns (out (B, H, Tq, 64) on the CPU, the
     whole guarded output buffer on the CPU as float, a bool tensor of the same shape marking what the op may write)."""
     from cosyvoice_amd import ops
     B, Hh, Hkv, Tq, Tk, lay = c["B"], c["H"], c["Hkv"], c["Tq"], c["Tk"], c["layout"]
@@ -239,7 +239,7 @@ def _launch(c, dt, q, k, v, bias, ok):
         Vt[b, :, :, :klen[b]] = vd[b, :, :klen[b]].transpose(1, 2)
     nb = 1 if kw["o_bs"] == 0 else B
     out = H.nan_like((nb * rows_o + (2 if lay == "prefill" else 0), kw["ldo"]), dt)
-    ops.attention(Q, K, Vt, out, **kw)
+    ops.attention(Q, K, Vt, out, mfma=mfma, waves=waves, **kw)
     torch.cuda.synchronize()
     o = out.cpu().float()
     may = torch.zeros_like(o, dtype=torch.bool)
@@ -257,13 +257,11 @@ VARIANTS = [("16", "4"), ("16", "2"), ("32", "4"), ("32", "2"), ("64", "4"), ("6
 @pytest.mark.parametrize("mfma,waves", VARIANTS, ids=[f"mfma{m}-waves{w}" for m, w in VARIANTS])
 @pytest.mark.parametrize("dt", DTS, ids=["bf16", "f16"])
 @pytest.mark.parametrize("name", NAMES)
-def test_attention_op(name, dt, mfma, waves, monkeypatch):
-    monkeypatch.setenv("CV_ATTN_MFMA", mfma)
-    monkeypatch.setenv("CV_ATTN_WAVES", waves)
+def test_attention_op(name, dt, mfma, waves):
     c = CASE_BY_NAME[name]
     q, k, v, bias, ok = _data(name, dt)
     ref, bound = _reference(name, dt)
-    res, o, may = _launch(c, dt, q, k, v, bias, ok)
+    res, o, may = _launch(c, dt, q, k, v, bias, ok, int(mfma), int(waves))
     assert bool(torch.isnan(o[~may]).all()), f"{name}: cv_attention wrote outside [B][Tq][H * 64]"
     H.check(f"attention {name} [{dt}] mfma {mfma} waves {waves}", res, ref, bound)
     dead = ~ok.any(-1)                                                      # (B, Tq): rows without a visible key

@@ -163,9 +163,9 @@ def test_tall_gemm_tile_plain_and_swiglu(dt):
 @pytest.mark.parametrize("shape", ["auto", "4x1", "2x2", "2x1", "1x2", "1x1"])
 @pytest.mark.parametrize("Cin,Cout,k,dil,T,B", [(64, 64, 3, 1, 1000, 2), (64, 64, 11, 5, 777, 1), (128, 128, 7, 3, 601, 2),
                                                 (256, 256, 11, 5, 500, 1), (256, 256, 3, 1, 130, 3), (128, 64, 7, 1, 70, 2), (64, 192, 3, 3, 257, 1)])
-def test_conv_window_kernel_presplit(Cin, Cout, k, dil, T, B, shape, monkeypatch):
+def test_conv_window_kernel_presplit(Cin, Cout, k, dil, T, B, shape):
     """conv_win_kernel (stride-1 bf16x3 convs on pre-split operands: activation window in LDS, weights streamed L2 -> VGPR) against torch
-    fp32, and against gemm_kernel on the same launch (the default; the window kernel is opt-in, CV_CONV_WIN=1): both the fp32 output and the pre-split snake output, every
+    fp32, and against gemm_kernel on the same launch (the default; the window kernel is opt-in, cv_gemm_params.conv_win): both the fp32 output and the pre-split snake output, every
     workgroup shape, ragged row / column tails, zero padding on both sides, residual + scale epilogue."""
     from cosyvoice_amd import ops, _lib as L
     from cosyvoice_amd.hift import _presplit
@@ -184,14 +184,12 @@ def test_conv_window_kernel_presplit(Cin, Cout, k, dil, T, B, shape, monkeypatch
     ref = (F.conv1d(xv.double().transpose(1, 2), wv.double(), bias.double(), dilation=dil, padding=pad).transpose(1, 2) + res.double()) * 0.5
     sn = ref + (1.0 / (alpha.double() + 1e-9)) * torch.sin(ref * alpha.double()) ** 2
     outs = {}
+    code = 1 if shape == "auto" else 10 * int(shape[0]) + int(shape[2])   # conv_win: 1 = automatic shape, 10 WM + WN = forced
     for win in ("1", "0"):
-        monkeypatch.setenv("CV_CONV_WIN", win)
-        if shape != "auto":
-            monkeypatch.setenv("CV_CONV_WIN_SHAPE", shape)
         o32 = torch.full((B, T, Cout), float("nan"), device=dev)
         oa = torch.full((B, T, Cout), float("nan"), device=dev)
         ops.conv1d_cl(xs, Ws, k, dilation=dil, pad_left=pad, bias=bias, res=res, out_scale=0.5, act=ops.ACT_SNAKE, act_param=alpha,
-                      out_f32=o32, out_act=oa, dtype=L.CV_F32X3, x3_flags=7)
+                      out_f32=o32, out_act=oa, dtype=L.CV_F32X3, x3_flags=7, conv_win=code if win == "1" else 0)
         torch.cuda.synchronize()
         outs[win] = (o32.clone(), _unsplit(oa.cpu()).to(dev))
         # bf16x3 drops the lo*lo term: relative 2^-16 per product, fp32 accumulation

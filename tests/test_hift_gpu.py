@@ -124,13 +124,29 @@ def test_stage_abi_decode_equals_python_composed_decode(tag, dt, mode):
     w_py = m.decode(mel, s).clone()
     torch.cuda.synchronize()
     assert torch.isfinite(w_abi).all() and w_abi.abs().max().item() > 0 and torch.equal(w_abi, w_py)
+    if (tag, dt, mode) != ("v2", torch.float32, "bf16x3"):
+        return
+    # conv_win reaches both compositions: cv_hift_conv.conv_win -> the launch (stages.hip hconv) and HiFTGenerator._conv -> ops.gemm.  v2 has
+    # 256- and 128-channel stages, where the window kernel and the implicit GEMM differ by fp32 re-association: a side that dropped the
+    # field would run the other kernel and break bit-identity.
+    from cosyvoice_amd import ops
+    m = HiFTGenerator(cfg, dtype=dt, f32_products=mode, conv_win=1).load_state_dict(hift_state_dict(cfg))
+    assert m.use_stage_abi and m.presplit
+    w_abi = m.decode(mel, s).clone()
+    m.use_stage_abi = False
+    w_py = m.decode(mel, s).clone()
+    torch.cuda.synchronize()
+    assert torch.isfinite(w_abi).all() and w_abi.abs().max().item() > 0 and torch.equal(w_abi, w_py)
+    with ops.Recorder() as rec:   # the parameter blocks of the Python-composed decode (recorded, not launched)
+        m.decode(mel, s)
+    assert any(name == "cv_gemm" and p.conv_win == 1 for name, p in rec.calls)
 
 
 @pytest.mark.parametrize("tag", ["tiny", "v2"])
 def test_presplit_storage_is_bit_identical(tag, monkeypatch):
     """bf16x3 decoder convs with PRE-SPLIT activation / weight storage (hi / lo bf16 planes per 4 values, written once by the producing
     epilogue) against the plain bf16x3 launches that split every operand tile as it is staged: same hi / lo bits, same MFMAs — bit-identical
-    on the implicit-GEMM kernel (the default).  The opt-in activation-window kernel (CV_CONV_WIN=1) sums chunk-major (64 channels at a time,
+    on the implicit-GEMM kernel (the default).  The opt-in activation-window kernel (conv_win=1) sums chunk-major (64 channels at a time,
     then taps) instead of tap-major: same products, fp32 re-association only."""
     from cosyvoice_amd.hift import HiFTGenerator
     cfg = CFGS[tag]
@@ -142,8 +158,7 @@ def test_presplit_storage_is_bit_identical(tag, monkeypatch):
     outs = {}
     for flag, win in (("1", "0"), ("0", "0"), ("1", "1")):
         monkeypatch.setenv("CV_HIFT_PRESPLIT", flag)
-        monkeypatch.setenv("CV_CONV_WIN", win)
-        m = HiFTGenerator(cfg, dtype=torch.float32, f32_products="bf16x3").load_state_dict(sd)
+        m = HiFTGenerator(cfg, dtype=torch.float32, f32_products="bf16x3", conv_win=int(win)).load_state_dict(sd)
         assert m.presplit == (flag == "1")
         outs[flag + win] = m.decode(mel, s).clone()
     torch.cuda.synchronize()

@@ -5,8 +5,6 @@ LN, Linear + exact-erf GELU + Linear + residual), and the fused estimator agains
 
 Tolerances: operands (LN output, GELU output, weights) are 16-bit with fp32 accumulation; the fp32 reference rounds the same
 intermediates to the operand type, so what remains is accumulation order and the erfc polynomial (|err| <= 1.5e-7)."""
-import os
-
 import pytest
 import torch
 import torch.nn.functional as F
@@ -37,9 +35,8 @@ def _packed(w, dt):
 @pytest.mark.parametrize("dt", [torch.float16, torch.bfloat16])
 @pytest.mark.parametrize("R,T", [(2, 150), (1, 64), (3, 1)])
 @pytest.mark.parametrize("mt", ["4", "3", "2", "1"])
-def test_head_vs_torch(dt, R, T, mt, monkeypatch):
+def test_head_vs_torch(dt, R, T, mt):
     from cosyvoice_amd import ops
-    monkeypatch.setenv("CV_TBLOCK_MT", mt)   # rows per workgroup = 16 MT
     w = _weights(dt)
     pk = _packed(w, dt)
     g = torch.Generator().manual_seed(1)
@@ -48,6 +45,7 @@ def test_head_vs_torch(dt, R, T, mt, monkeypatch):
     qk = torch.zeros(R, T, 2 * INNER, device="cuda", dtype=dt)
     vt = torch.zeros(R, INNER // 64, 64, Tp, device="cuda", dtype=dt)
     p = ops.tblock_params(x, R, T, 1e-5, dt)
+    p.mt = int(mt)   # rows per workgroup = 16 MT
     p.g1, p.b1n, p.wqkv_p = w["g1"].data_ptr(), w["b1"].data_ptr(), pk["wqkv_p"].data_ptr()
     p.qk, p.ldqk, p.vt, p.vt_ld = qk.data_ptr(), 2 * INNER, vt.data_ptr(), Tp
     ops.tblock_head(p)
@@ -75,9 +73,8 @@ def _tail_ref(x, ao, w, dt):
 @pytest.mark.parametrize("R,T", [(2, 150), (1, 64), (2, 65)])
 @pytest.mark.parametrize("outproj", [True, False])
 @pytest.mark.parametrize("mt", ["4", "3", "2", "1"])
-def test_tail_vs_torch(dt, R, T, outproj, mt, monkeypatch):
+def test_tail_vs_torch(dt, R, T, outproj, mt):
     from cosyvoice_amd import ops
-    monkeypatch.setenv("CV_TBLOCK_MT", mt)
     w = _weights(dt, seed=2)
     pk = _packed(w, dt)
     g = torch.Generator().manual_seed(3)
@@ -87,6 +84,7 @@ def test_tail_vs_torch(dt, R, T, outproj, mt, monkeypatch):
     xk = x.clone()
     oa = torch.zeros(R, T, 2 * C, device="cuda", dtype=dt)
     p = ops.tblock_params(xk, R, T, 1e-5, dt)
+    p.mt = int(mt)
     if outproj:
         p.ao, p.ldao, p.wo_p, p.bo = ao.data_ptr(), INNER, pk["wo_p"].data_ptr(), w["bo"].data_ptr()
     p.g3, p.b3n = w["g3"].data_ptr(), w["b3"].data_ptr()
@@ -105,13 +103,12 @@ def test_tail_vs_torch(dt, R, T, outproj, mt, monkeypatch):
 @pytest.mark.parametrize("dt", [torch.float16, torch.bfloat16])
 @pytest.mark.parametrize("R,T", [(2, 150), (1, 64), (2, 65), (3, 1)])
 @pytest.mark.parametrize("mt", ["4", "3", "2", "1"])
-def test_tail_head_fused_equals_tail_then_head(dt, R, T, mt, monkeypatch):
+def test_tail_head_fused_equals_tail_then_head(dt, R, T, mt):
     """cv_tblock_tail_head (tail of block i + head of block i + 1 in one launch) against cv_tblock_tail followed by cv_tblock_head:
     the fp32 residual stream x must be bit-identical (same accumulators, stored once); [Q | K] and V^T may differ by the summation
     order of the LayerNorm statistics (taken from the accumulators instead of re-read rows) — a 16-bit ulp here and there — and both
     are checked against torch fp32."""
     from cosyvoice_amd import ops
-    monkeypatch.setenv("CV_TBLOCK_MT", mt)
     w, w2 = _weights(dt, seed=2), _weights(dt, seed=7)       # block i, block i + 1
     pk, pk2 = _packed(w, dt), _packed(w2, dt)
     g = torch.Generator().manual_seed(3)
@@ -124,6 +121,7 @@ def test_tail_head_fused_equals_tail_then_head(dt, R, T, mt, monkeypatch):
         qk = torch.zeros(R, T, 2 * INNER, device="cuda", dtype=dt)
         vt = torch.zeros(R, INNER // 64, 64, Tp, device="cuda", dtype=dt)
         p = ops.tblock_params(xk, R, T, 1e-5, dt)
+        p.mt = int(mt)
         p.ao, p.ldao, p.wo_p, p.bo = ao.data_ptr(), INNER, pk["wo_p"].data_ptr(), w["bo"].data_ptr()
         p.g3, p.b3n = w["g3"].data_ptr(), w["b3"].data_ptr()
         p.w1_p, p.bf1, p.w2_p, p.bf2 = pk["w1_p"].data_ptr(), w["bf1"].data_ptr(), pk["w2_p"].data_ptr(), w["bf2"].data_ptr()
@@ -285,7 +283,7 @@ def test_resblock_vs_torch(dt, tol, cin, T):
     p.wr_p, p.br = keep[2].data_ptr(), keep[10].data_ptr()
     p.out, p.ldo, p.eps = outd.data_ptr(), Cc, 1e-5
     for mt in ("4", "3", "2", "1"):
-        os.environ["CV_TBLOCK_MT"] = mt
+        p.mt = int(mt)
         h1d.zero_(); outd.zero_()
         ops._issue("cv_resblock_conv1", p)
         ops._issue("cv_resblock_conv2", p)
@@ -294,7 +292,6 @@ def test_resblock_vs_torch(dt, tol, cin, T):
         e2 = (outd.cpu() - ref).abs().max().item()
         print(f"resblock[{dt}, cin={cin}, T={T}, MT={mt}]: h1 Linf {e1:.3e}  out Linf {e2:.3e} (values ~ {ref.abs().mean().item():.2f})")
         assert e1 < tol and e2 < tol
-    os.environ.pop("CV_TBLOCK_MT", None)
 
 
 @pytest.mark.parametrize("ragged", [False, True])

@@ -1,6 +1,6 @@
 """BASELINE config C2 / batch-1 flow: ONE utterance through the flow stage (encoder + 10 CFG Euler steps as one hipGraph), at
-T = 500 (250 tokens, no prompt: C2), T = 650 (C1: 75-token prompt + 250) and T = 1000 (C4's utterance: 250 + 250), all CUs.
-CV_TBLOCK_MT / CV_ATTN_WAVES override the tile choices (tuning).  Prints ms and TFLOP/s on SURVEY.md §8d's flop counts."""
+T = 500 (250 tokens, no prompt: C2), T = 650 (C1: 75-token prompt + 250) and T = 1000 (C4's utterance: 250 + 250), all CUs, with the
+library's own tile choices.  Prints ms and TFLOP/s on SURVEY.md §8d's flop counts."""
 import os, sys, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from cosyvoice_amd.config import FlowConfig
@@ -25,5 +25,5 @@ for n_p, n_g, tf in ((0, 250, 1.895), (75, 250, 2.687), (250, 250, 4.937)):
     for _ in range(n):
         flow.inference_batch(tok, ptok, pfeat, emb)
     torch.cuda.synchronize(); ms = (time.perf_counter() - t0) / n * 1e3
-    print(f"flow batch 1, T={2 * (n_p + n_g)} [MT={os.environ.get('CV_TBLOCK_MT', 'auto')}, attn waves={os.environ.get('CV_ATTN_WAVES', 'auto')}]: "
+    print(f"flow batch 1, T={2 * (n_p + n_g)}: "
           f"{ms:.2f} ms  {tf / ms * 1e3:.0f} TFLOP/s ({tf / ms * 1e3 / 2500:.4f} of 2.5 PF)", flush=True)

@@ -1,5 +1,5 @@
-"""Prefill (+ first token) wall time of Qwen2LM for NB utterances (env NB, default 8) and a forced GEMM tile (env CV_GEMM_TILE): what the
-decode jobs of tts_batches put on the flow CUs per job.  B = 8: 6.7 ms, B = 32: 18.8 ms (16.2 with the 8-wave 128x128 tile)."""
+"""Prefill (+ first token) wall time of Qwen2LM for NB utterances (env NB, default 8), with the GEMM tiles cv_gemm picks itself: what the
+decode jobs of tts_batches put on the flow CUs per job.  B = 8: 6.7 ms, B = 32: 16.2 ms (18.8 before the 8-wave 128x128 tile for tall GEMMs)."""
 import os, sys, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench as B
@@ -16,4 +16,4 @@ def run(): llm.generate_batch(t, [pt] * nb, [ps] * nb, forced=forced, max_steps=
 for _ in range(3): run()
 torch.cuda.synchronize(); t0 = time.perf_counter()
 for _ in range(5): run()
-torch.cuda.synchronize(); print(f"prefill(+1 step) B={nb} tile={os.environ.get('CV_GEMM_TILE')}: {(time.perf_counter()-t0)/5*1e3:.2f} ms")
+torch.cuda.synchronize(); print(f"prefill(+1 step) B={nb}: {(time.perf_counter()-t0)/5*1e3:.2f} ms")
