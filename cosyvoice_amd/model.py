@@ -31,6 +31,11 @@ def fade_in_out(fade_in_mel, fade_out_mel, window):
     return fade_in_mel.to(device)
 
 
+def _ragged_prompts(b):
+    """A batch whose flow prompts are per-utterance lists (different lengths) instead of stacked (B, Np) / (B, Tp, 80) tensors."""
+    return isinstance(b["flow_prompt_speech_tokens"], (list, tuple))
+
+
 class CosyVoice2Model:
     def __init__(self, llm, flow, hift, fp16: bool = False):
         self.device = torch.device("cuda")
@@ -279,7 +284,9 @@ class CosyVoice2Model:
                   flow_prompt_speech_tokens: torch.Tensor, prompt_speech_feats: torch.Tensor, flow_embeddings: torch.Tensor,
                   forced: Optional[List[List[int]]] = None, to_host: bool = True):
         """B utterances (texts / prompts of any lengths) through LLM -> flow -> HiFT.  Returns wav (B,S) when all sequences
-        generated the same number of tokens (teacher-forced), else a list of B waveforms."""
+        generated the same number of tokens (teacher-forced), else a list of B waveforms.  ``flow_prompt_speech_tokens`` /
+        ``prompt_speech_feats`` may be lists of per-utterance (Np_b,) / (2 * Np_b, 80) tensors (prompts of different lengths): the
+        result is then always a list."""
         toks = self.llm.generate_batch(texts, prompt_texts, llm_prompt_speech_tokens, forced=forced)
         wav = self._flow_hift(dict(flow_prompt_speech_tokens=flow_prompt_speech_tokens, prompt_speech_feats=prompt_speech_feats,
                                    flow_embeddings=flow_embeddings), toks)
@@ -412,10 +419,12 @@ class CosyVoice2Model:
         """Flow + HiFT of one batch.  Equal generated lengths (teacher-forced runs, the benchmark): one batched pass ->
         wav (B, S).  Free-running sampling ends every sequence at its own step: the flow and the vocoder then each run once over
         the ragged batch (rows padded to the longest, every stage bounded by the row's own length: exact per utterance) -> list of
-        B waveforms (S_b,).  ``ragged_hift = False``: the vocoder runs per utterance instead (the cross-check)."""
+        B waveforms (S_b,).  ``ragged_hift = False``: the vocoder runs per utterance instead (the cross-check).  Prompts of different
+        lengths (``flow_prompt_speech_tokens`` / ``prompt_speech_feats`` given as per-utterance lists, frontend.PromptFrontEnd.batch)
+        take the ragged path whatever the generated lengths."""
         n = len(toks[0])
         zero = torch.zeros(1, 1, 0)
-        if all(len(t) == n for t in toks):
+        if all(len(t) == n for t in toks) and not _ragged_prompts(b):
             tok = torch.tensor(toks, dtype=torch.int32, device=self.device)
             mel = self.flow.inference_batch(tok, b["flow_prompt_speech_tokens"], b["prompt_speech_feats"], b["flow_embeddings"])
             wav, _ = self.hift.inference(speech_feat=mel.contiguous(), cache_source=zero)
@@ -547,7 +556,7 @@ class CosyVoice2Model:
             if est is not None:   # tile sizes of the row-block kernels (and the solver graph that bakes them in) follow the CUs of the stream
                 est.cu_budget = 0 if stream is flow_full else (32 - k) * 8
             n_t = len(toks[0])
-            equal = all(len(t) == n_t for t in toks)
+            equal = all(len(t) == n_t for t in toks) and not _ragged_prompts(grp[0])
             if self.overlap_hift and (equal or self.ragged_hift):
                 with torch.no_grad(), torch.cuda.stream(stream):
                     for r in ready_evs:
@@ -590,6 +599,8 @@ class CosyVoice2Model:
         flow_q, flow_cv, flow_state = deque(), threading.Condition(), {"closed": False, "abort": False}
 
         def same_layout(a, c):
+            if _ragged_prompts(a) or _ragged_prompts(c):   # per-utterance prompt lists: such a batch is a flow pass of its own
+                return False
             return all(a[k_].shape[1:] == c[k_].shape[1:] for k_ in keys)
 
         def flow_worker():
