@@ -284,6 +284,57 @@ EXPORTS = ["cv_version", "cv_arch", "cv_gemm", "cv_layernorm", "cv_attention",
            "cv_hift_decode_graph_create", "cv_spk_power", "cv_spk_log_cmn", "cv_sizeof_spk_conv_params", "cv_spk_conv",
            "cv_spk_cam_gate", "cv_spk_stats_pool"]
 
+# ---- speaker encoder v2 (include/cosyvoice_amd_style.h, csrc/style.hip): its own header, export list and size handshake
+class WnLayerParams(C.Structure):
+    _fields_ = [
+        ("B", _i32), ("T", _i32), ("C", _i32), ("taps", _i32),
+        ("len", _vp),
+        ("x", _vp), ("x_bs", _i64), ("ldx", _i32),
+        ("w_in", _vp), ("b_in", _vp), ("w_rs", _vp), ("b_rs", _vp),
+        ("n_rs", _i32), ("skip_init", _i32),
+        ("x_out", _vp), ("xo_bs", _i64), ("ldxo", _i32),
+        ("skip", _vp), ("skip_bs", _i64), ("ldskip", _i32),
+    ]
+
+
+class GluConvParams(C.Structure):
+    _fields_ = [
+        ("B", _i32), ("T", _i32), ("C", _i32), ("taps", _i32),
+        ("len", _vp),
+        ("x", _vp), ("x_bs", _i64), ("ldx", _i32),
+        ("w", _vp), ("bias", _vp),
+        ("y", _vp), ("y_bs", _i64), ("ldy", _i32),
+    ]
+
+
+STYLE_EXPORTS = ["cv_sizeof_wn_layer_params", "cv_wn_layer", "cv_wn_gate", "cv_sizeof_glu_conv_params", "cv_glu_conv", "cv_gst_attention",
+                 "cv_style_attention", "cv_posterior_sample", "cv_masked_mean"]
+
+_style_lib = None
+
+
+def style_lib():
+    """The library with the style entry points bound: checks that it exports every STYLE_EXPORTS name and that the two parameter
+    blocks have the size the C side compiled (first use only)."""
+    global _style_lib
+    if _style_lib is None:
+        so = lib()
+        for name in STYLE_EXPORTS:
+            if not hasattr(so, name):
+                raise RuntimeError(f"{LIB_PATH} does not export {name}: rebuild it with `python -m cosyvoice_amd.build`")
+        for name, st in (("wn_layer", WnLayerParams), ("glu_conv", GluConvParams)):
+            fn = getattr(so, f"cv_sizeof_{name}_params")
+            if fn() != C.sizeof(st):
+                raise RuntimeError(f"ABI mismatch for cv_{name}_params: C {fn()} vs ctypes {C.sizeof(st)}")
+        so.cv_wn_gate.argtypes = [_vp, _i32, _vp, _i32, _i32, _i32, _vp]
+        so.cv_gst_attention.argtypes = [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp]
+        so.cv_style_attention.argtypes = [_vp, _vp, _vp, _i64, _i32, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _f32, _vp]
+        so.cv_posterior_sample.argtypes = [_vp, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp]
+        so.cv_masked_mean.argtypes = [_vp, _i64, _i32, _vp, _i32, _i32, _i32, _vp, _i32, _vp]
+        _style_lib = so
+    return _style_lib
+
+
 TORCH_DT = {torch.float32: CV_F32, torch.bfloat16: CV_BF16, torch.float16: CV_F16}
 DT_TORCH = {v: k for k, v in TORCH_DT.items()}
 

@@ -380,10 +380,14 @@ class PromptFrontEnd:
     ``speaker.CAMPPlus``.  Text and speech tokens come in as int tensors (the tokenizers and the speech-tokenizer model are not part
     of this package).  ``batch`` serves ``tts_batch`` / ``tts_batches``: B prompts of any lengths through ONE resampling launch, one
     ragged mel pass and one speaker-embedding graph; all lengths follow from the sample counts on the host, so nothing waits for
-    the device between the upload and the returned tensors."""
+    the device between the upload and the returned tensors.
 
-    def __init__(self, feat_extractor, campplus, device="cuda"):
-        self.feat_extractor, self.campplus = feat_extractor, campplus
+    ``speaker_encoder`` (optional): a loaded ``style.SpeakerEmbedding`` / ``SpeakerEmbeddingWoPostEnc``.  When given, the embedding of
+    the dicts and of ``batch`` is its 512-d vector of the 24 kHz prompt (what the recipes with ``spk_embed_dim: 512`` condition on)
+    instead of the 192-d CAM++ vector; its posterior noise is drawn per call, as the reference draws it."""
+
+    def __init__(self, feat_extractor, campplus, device="cuda", speaker_encoder=None):
+        self.feat_extractor, self.campplus, self.speaker_encoder = feat_extractor, campplus, speaker_encoder
         self.device = torch.device(device)
         self._resamplers = {}
 
@@ -395,11 +399,16 @@ class PromptFrontEnd:
 
     @torch.no_grad()
     def prompt_features(self, prompt_speech_16k, resample_rate):
-        """list of 16 kHz waveforms ((S,) or (1, S)) -> (per utterance prompt mel (1, T_b, 80), embeddings (B, 192)), on the device."""
+        """list of 16 kHz waveforms ((S,) or (1, S)) -> (per utterance prompt mel (1, T_b, 80), embeddings (B, 192) — (B, 512) with a
+        ``speaker_encoder``), on the device."""
         waves = [torch.as_tensor(w).reshape(-1) for w in prompt_speech_16k]
         buf, lens = self.resampler(resample_rate)(waves)
         mel, frames = self.feat_extractor.ragged((buf, lens))
-        emb = self.campplus.extract_spk_embedding(waves)
+        if self.speaker_encoder is None:
+            emb = self.campplus.extract_spk_embedding(waves)
+        else:
+            b24, l24 = (buf, lens) if resample_rate == 24000 else self.resampler(24000)(waves)
+            emb = self.speaker_encoder(b24, wave_lengths=l24)
         mel = mel.transpose(1, 2)                                           # (B, T_max, 80)
         return [mel[b:b + 1, :frames[b]] for b in range(len(waves))], emb
 

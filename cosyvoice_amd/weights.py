@@ -538,3 +538,93 @@ def campplus_state_dict(seed: int = 1986) -> Dict[str, torch.Tensor]:
     specs = campplus_specs()
     sd = materialize([sp for sp in specs if sp[2] != "count"], seed)
     return {k: (torch.zeros(shape, dtype=torch.int64) if kind == "count" else sd[k]) for k, shape, kind, _ in specs}
+
+
+# --------------------------------------------------------------------------- speaker encoder v2 (512-d)
+# SpeakerEmbedding (speaker/speaker_encoder.py:119-221): enc_q = PosteriorEncoder(513, 512, 512, 5, 1, 16) (posterior_encoder.py:24-27,
+# WN modules.py:157-188), speaker_encoder = CAMPPlus(80, 192), style_encoder = StyleEncoder_v2(512, 256, 512, 5, 4, num_layers=6)
+# (style_encoder.py:40-70), gst = GlobalStyleTokens_v2(4096, 512, 8, 6) (:131-146), speaker_adapter = StyleFuser(512, 192, "Add") (:165).
+SPK2_SPEC, SPK2_HIDDEN, SPK2_WN_LAYERS, SPK2_WN_K = 513, 512, 16, 5
+SPK2_STYLE_HIDDEN, SPK2_STYLE_HEADS, SPK2_STYLE_LAYERS, SPK2_STYLE_K = 256, 4, 6, 5
+SPK2_GST_TOKENS, SPK2_GST_HEADS, SPK2_GST_LAYERS, SPK2_DIM = 4096, 8, 6, 512
+# Gains over nn.Linear's own initialiser U(+-1/sqrt(fan_in)).  At that initialiser every softmax of the model is uniform (a wrong
+# score moves nothing); these put the mean entropy of every style self-attention layer and every style-token layer at least one nat
+# away from both uniform and one-hot on the committed cases (asserted where the goldens are minted, tests/golden/make_golden_style.py).
+SPK2_GAINS = {"in_fc": 2.0, "spectral": 2.4, "mha_qk": 3.0, "gst_qk": 6.0, "gst_v": 5.0}
+
+
+def _lin_u(specs, name, out_f, in_f, bias=True, gain=1.0):
+    specs.append((f"{name}.weight", (out_f, in_f), "uniform", gain / math.sqrt(in_f)))
+    if bias:
+        specs.append((f"{name}.bias", (out_f,), "uniform", 1.0 / math.sqrt(in_f)))
+
+
+def _wn_conv_bgv(specs, name, cout, cin, k):
+    """Legacy weight_norm registration order: bias, weight_g, weight_v."""
+    specs.append((f"{name}.bias", (cout,), "normal", 0.02))
+    specs.append((f"{name}.weight_g", (cout, 1, 1), "wn_g", 0.0))
+    specs.append((f"{name}.weight_v", (cout, cin, k), "normal", 1.0 / math.sqrt(cin * k)))
+
+
+def posterior_encoder_specs(prefix: str = "enc_q.") -> List[Spec]:
+    s: List[Spec] = []
+    H = SPK2_HIDDEN
+    _conv(s, f"{prefix}pre", H, SPK2_SPEC, 1)
+    for i in range(SPK2_WN_LAYERS):
+        _wn_conv_bgv(s, f"{prefix}enc.in_layers.{i}", 2 * H, H, SPK2_WN_K)
+    for i in range(SPK2_WN_LAYERS):
+        _wn_conv_bgv(s, f"{prefix}enc.res_skip_layers.{i}", 2 * H if i < SPK2_WN_LAYERS - 1 else H, H, 1)
+    _conv(s, f"{prefix}proj", 2 * H, H, 1, gain=0.1)
+    return s
+
+
+def style_specs(gains=None) -> List[Spec]:
+    """style_encoder.*, gst.* and speaker_adapter.* in the reference's key order."""
+    g = dict(SPK2_GAINS, **(gains or {}))
+    s: List[Spec] = []
+    D, H, L = SPK2_STYLE_HIDDEN, SPK2_HIDDEN, SPK2_STYLE_LAYERS
+    for i in range(L):
+        _lin_u(s, f"style_encoder.spectral_layers.{i}.0.fc", D, D, gain=g["spectral"])
+        _lin_u(s, f"style_encoder.spectral_layers.{i}.3.fc", D, D, gain=g["spectral"])
+    for i in range(L):
+        for j in (0, 1):
+            n = f"style_encoder.temporal_layers.{i}.{j}.conv1.conv"
+            s.append((f"{n}.weight", (2 * D, D, SPK2_STYLE_K), "uniform", 1.0 / math.sqrt(D * SPK2_STYLE_K)))
+            s.append((f"{n}.bias", (2 * D,), "uniform", 1.0 / math.sqrt(D * SPK2_STYLE_K)))
+    for i in range(L):
+        n = f"style_encoder.attn_layers.{i}"
+        _lin_u(s, f"{n}.w_qs", D, D, gain=g["mha_qk"])
+        _lin_u(s, f"{n}.w_ks", D, D, gain=g["mha_qk"])
+        _lin_u(s, f"{n}.w_vs", D, D)
+        _lin_u(s, f"{n}.fc", D, D)
+    _lin_u(s, "style_encoder.in_fc.fc", D, H, gain=g["in_fc"])
+    _lin_u(s, "style_encoder.fc.fc", SPK2_DIM, D)
+    dk = SPK2_DIM // SPK2_GST_HEADS
+    for i in range(SPK2_GST_LAYERS):
+        s.append((f"gst.embeds.{i}", (SPK2_GST_TOKENS, dk), "normal", 0.5))
+    for i in range(SPK2_GST_LAYERS):
+        n = f"gst.attentions.{i}"
+        _lin_u(s, f"{n}.W_query", SPK2_DIM, SPK2_DIM, bias=False, gain=g["gst_qk"])
+        _lin_u(s, f"{n}.W_key", SPK2_DIM, dk, bias=False, gain=g["gst_qk"])
+        _lin_u(s, f"{n}.W_value", SPK2_DIM, dk, bias=False, gain=g["gst_v"])
+    _lin_u(s, "speaker_adapter.style_fuser", SPK2_DIM, CAMPPLUS_EMBED, bias=False)
+    return s
+
+
+def speaker_embedding_specs(post_enc: bool = True, gains=None) -> List[Spec]:
+    """Keys and shapes of SpeakerEmbedding (``post_enc``) / SpeakerEmbedding_wo_PostEnc (enc_q = nn.Linear(513, 512)) in the
+    reference's state-dict order: enc_q.*, speaker_encoder.* (CAM++), style_encoder.*, gst.*, speaker_adapter.*."""
+    s: List[Spec] = posterior_encoder_specs() if post_enc else []
+    if not post_enc:
+        _lin_u(s, "enc_q", SPK2_HIDDEN, SPK2_SPEC, gain=0.62)   # z at the scale the posterior encoder gives it
+    s += [("speaker_encoder." + k, shape, kind, p) for k, shape, kind, p in campplus_specs()]
+    return s + style_specs(gains)
+
+
+def speaker_embedding_state_dict(seed: int = 1986, post_enc: bool = True, gains=None) -> Dict[str, torch.Tensor]:
+    """Key-seeded, full-size (72.0 M state-dict elements, 71.9 M of them parameters) weights of the 512-d speaker encoder; the CAM++ tensors are those of
+    ``campplus_state_dict(seed)`` under ``speaker_encoder.``."""
+    specs = speaker_embedding_specs(post_enc, gains)
+    cam = campplus_state_dict(seed)
+    sd = materialize([sp for sp in specs if not sp[0].startswith("speaker_encoder.")], seed)
+    return {k: (cam[k[len("speaker_encoder."):]] if k.startswith("speaker_encoder.") else sd[k]) for k, _, _, _ in specs}
