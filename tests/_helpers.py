@@ -267,3 +267,149 @@ def rmsnorm_ref64(v, gamma, eps, dt):
     dim = v.shape[-1]
     ref = v * torch.rsqrt((v * v).mean(-1, keepdim=True) + torch.tensor(eps, dtype=torch.float32).double()) * g
     return ref, (dim / 2 + 5) * EPS32 * ref.abs() + 0.5 * ulp(ref, dt)
+
+
+# ----------------------------------------------------------------------------- flow estimator row-block kernels (csrc/flowblock.hip)
+AS_ERFC_CAP = 1.5e-7    # Abramowitz-Stegun 7.1.26, the |error| the kernel's gelu_erf comment states for its erfc polynomial
+ROW_KINDS = ("x30", "offset", "const", "zero")
+
+
+def flow_rows(R, T, width, g):
+    """(R, T, width) fp32 activations: ordinary rows 2 N(0, 1) + 0.3, and in every sequence r the four special rows ROW_KINDS[(r + j) % 4] at
+    rows (T - 1, 0, T // 2, 1)[j] (a position that repeats keeps its first kind: T = 1 holds x30 / offset / const in its three sequences):
+    x30 = an ordinary row times 30, offset = an ordinary row + 100, const = c + 1e-3 N(0, 1) with c = 0.5 + 0.25 r (variance 1e-6: eps = 1e-5
+    dominates), zero = all zeros.  The last row of a sequence and the first of the next are therefore always of different kinds."""
+    x = torch.randn(R, T, width, generator=g) * 2 + 0.3
+    for r in range(R):
+        seen = set()
+        for j, t in enumerate((T - 1, 0, T // 2, 1)):
+            if t in seen or t >= T:
+                continue
+            seen.add(t)
+            kind = ROW_KINDS[(r + j) % 4]
+            if kind == "x30":
+                x[r, t] *= 30.0
+            elif kind == "offset":
+                x[r, t] += 100.0
+            elif kind == "const":
+                x[r, t] = (0.5 + 0.25 * r) + 1e-3 * torch.randn(width, generator=g)
+            else:
+                x[r, t] = 0.0
+    return x
+
+
+def bits(t):
+    """The tensor's storage as integers: equality that tells NaN payloads and signed zeros apart."""
+    t = t.contiguous()
+    return t.view({4: torch.int32, 2: torch.int16}[t.element_size()])
+
+
+def window_only(name, buf, rows, c0, c1):
+    """buf (rows + guard, ld) was NaN everywhere before the op: after it only [0, rows) x [c0, c1) may hold anything else."""
+    m = torch.isnan(buf.float())
+    assert bool(m[rows:].all()), f"{name}: guard rows past the last sequence were written"
+    assert bool(m[:rows, :c0].all()) and bool(m[:rows, c1:].all()), f"{name}: pitch slack outside columns [{c0}, {c1}) was written"
+
+
+def carry16(y, b, dt):
+    """Interval of a 16-bit intermediate carried UNROUNDED in float64: its fp32 error bound b plus half an ulp of ``dt`` at the largest value
+    the kernel may have rounded (|y| + b)."""
+    return b + 0.5 * ulp(y.abs() + b, dt)
+
+
+def ln_ref64(x, dx, gamma, beta, eps):
+    """LayerNorm over the last dimension in float64 and the fp32 bound of flowblock.hip's arithmetic (one fp32 mean, then centred squares; derived
+    in the module docstring of tests/test_flowblock_ops_gpu.py).  x: the rows as the kernel holds them up to the element-wise interval dx (None:
+    rows read from memory, exact).  Returns y (unrounded) and its bound (without the rounding to a 16-bit type: carry16)."""
+    x, g, b = x.double(), gamma.double(), beta.double()
+    n = x.shape[-1]
+    dx = torch.zeros_like(x) if dx is None else dx.double()
+    eps64 = torch.tensor(eps, dtype=torch.float32).double()
+    s = x.sum(-1, keepdim=True)
+    d = x - s / n
+    q = (d * d).sum(-1, keepdim=True)
+    v = q / n + eps64
+    rstd = torch.rsqrt(v)
+    y = d * rstd * g + b
+    dmu = sum_bound(n, x.abs().sum(-1, keepdim=True), s, torch.float32) / n               # rule 2 on the row sum: ~ (n + 2) 2^-23 mean|x_row|
+    dd = dmu + dx + dx.mean(-1, keepdim=True) + 0.5 * ulp(d, torch.float32)               # x_i - mean: both errors and one rounding
+    dq = sum_bound(n, q, q, torch.float32) + 2.0 * (d.abs() * dd).sum(-1, keepdim=True)   # rule 2 on the squares + d(d^2) = 2 |d| dd
+    rel = 0.5 * (dq / n + 0.5 * EPS32 * v) / v + 2.0 * EPS32                              # through v^-1/2; + eps rounds once; rsqrtf <= 2 ulp
+    first = g.abs() * rstd * (dd + d.abs() * rel) + 1.5 * EPS32 * ((d * rstd * g).abs() + b.abs())   # the last: two products and one sum
+    return y, 2.0 * first
+
+
+def ln_emulate(x, gamma, beta, eps, stats_from=None):
+    """fp32 torch: one mean, centred squares, rsqrt, (x - mean) rstd gamma + beta; stats_from: rows whose statistics are used instead."""
+    xs = x if stats_from is None else stats_from
+    n = x.shape[-1]
+    mean = xs.sum(-1, keepdim=True) * (1.0 / n)
+    ds = xs - mean
+    rstd = torch.rsqrt((ds * ds).sum(-1, keepdim=True) * (1.0 / n) + eps)
+    return (x - mean) * rstd * gamma + beta
+
+
+def gelu_ref64(x):
+    return 0.5 * x * torch.erfc(-x * 0.7071067811865476)       # x Phi(x) without the 1 - erf cancellation of the negative side
+
+
+def gelu_bound(pre, bpre, dt):
+    """exact-erf GELU of a pre-activation known to the element-wise interval bpre, rounded to ``dt``: ACT_LIPSCHITZ x bpre + rule 3 + the erfc
+    polynomial's stated cap 0.5 |x| 1.5e-7 (``b32``), + half an ulp; fp16: a value the kernel may hold below 2^-14 may be flushed to zero instead
+    of rounded gradually (+ |g| there).  Returns g (unrounded float64), the bound, and e32."""
+    import torch.nn.functional as F
+    g = gelu_ref64(pre)
+    p32 = pre.float()
+    e32 = (F.gelu(p32).double() - gelu_ref64(p32.double())).abs().max()
+    b32 = ACT_LIPSCHITZ["GELU"] * bpre + 4.0 * torch.maximum(e32, EPS32 * g.abs()) + 0.5 * pre.abs() * AS_ERFC_CAP
+    b = carry16(g, b32, dt)
+    if dt == torch.float16:
+        b = b + torch.where(g.abs() - b32 < 2.0 ** -14, g.abs(), torch.zeros_like(g))
+    return g, b, e32.item()
+
+
+def gelu_emulate(x):
+    """The kernel's gelu_erf in fp32 torch: relu(x) - 0.5 |x| erfc(|x| / sqrt 2), erfc by the A-S 7.1.26 polynomial, exp through exp2."""
+    ax = x.abs()
+    t = 1.0 / (ax * (0.3275911 * 0.70710678118654752) + 1.0)
+    e = torch.exp2(x * x * (-0.5 * 1.4426950408889634))
+    pl = 1.061405429 * t - 1.453152027
+    pl = pl * t + 1.421413741
+    pl = pl * t - 0.284496736
+    pl = pl * t + 0.254829592
+    return (-0.5 * ax) * (pl * t * e) + torch.clamp(x, min=0)
+
+
+def mish_ref64(x):
+    import torch.nn.functional as F
+    return x * torch.tanh(F.softplus(x, threshold=700.0))
+
+
+def mish_bound(y, by):
+    """Mish of a value known to the interval by, evaluated in fp32: ACT_LIPSCHITZ x by + rule 3.  Returns m (float64), the bound, e32."""
+    import torch.nn.functional as F
+    m = mish_ref64(y)
+    y32 = y.float()
+    e32 = (F.mish(y32).double() - mish_ref64(y32.double())).abs().max()
+    return m, ACT_LIPSCHITZ["MISH"] * by + 4.0 * torch.maximum(e32, EPS32 * m.abs()), e32.item()
+
+
+def mish_emulate(x):
+    """The kernel's mish_fast in fp32 torch: x w / (w + 2), w = e^x (e^x + 2), e^x = exp2(min(x, 20) log2 e)."""
+    n = torch.exp2(torch.clamp(x, max=20.0) * 1.4426950408889634)
+    w = n * (n + 2.0)
+    return x * w / (w + 2.0)
+
+
+def causal_conv3_64(a, w):
+    """Causal k = 3 conv (left padding 2) of channels-last a (R, T, Ci) with w (Co, Ci, 3) in a's dtype (float64 for the references)."""
+    import torch.nn.functional as F
+    return F.conv1d(F.pad(a.transpose(1, 2), (2, 0)), w).transpose(1, 2)
+
+
+def worst_ratio(got, ref, bound):
+    """max err / bound, a non-finite output counting as infinite: by how much an injected fault misses."""
+    got, ref, bound = got.double(), ref.double(), bound.double()
+    if not bool(torch.isfinite(got).all()):
+        return float("inf")
+    return ((got - ref).abs() / bound.clamp_min(1e-300)).max().item()

@@ -112,6 +112,60 @@ def test_out_of_range_variant_fields_are_rejected_without_a_gpu():
         setattr(p, field, 0)
 
 
+def _flowblock_blocks():
+    """cv_tblock_params that pass every check of cv_tblock_head, cv_tblock_tail and cv_tblock_tail_head, and cv_resblock_params that pass those
+    of conv1 and conv2 (dummy aligned pointers, never dereferenced: nothing may be launched with them)."""
+    from cosyvoice_amd import _lib as L
+    t = L.TBlockParams()
+    t.dtype, t.R, t.T, t.C, t.inner, t.ff = L.CV_BF16, 1, 16, 256, 512, 1024
+    for f in ("x", "g1", "b1n", "wqkv_p", "qk", "vt", "ao", "wo_p", "bo", "g3", "b3n", "w1_p", "bf1", "w2_p", "bf2"):
+        setattr(t, f, 16)
+    t.ldx, t.eps, t.ldqk, t.vt_ld, t.ldao = 256, 1e-5, 1024, 16, 512
+    r = L.ResblockParams()
+    r.dtype, r.R, r.T, r.C, r.cin = L.CV_BF16, 1, 16, 256, 256
+    for f in ("a", "w1_p", "b1", "g1", "be1", "tadd", "h1", "w2_p", "b2", "g2", "be2", "wr_p", "br", "out"):
+        setattr(r, f, 16)
+    r.lda, r.ldh1, r.ldo, r.eps = 256, 256, 256, 1e-5
+    return t, r
+
+
+def test_flowblock_argument_contract_without_a_gpu():
+    """The row-block kernels' entry points (csrc/flowblock.hip) return CV_ERR_ARG / CV_ERR_UNSUPPORTED for what their kernels cannot take,
+    before anything is launched.  Every case changes only the fields named in a block that meets every other check of the entry point, and
+    restores them."""
+    from cosyvoice_amd import _lib as L
+    lib = L.lib()
+    null = ctypes.c_void_p(None)
+    ARG, UNSUPPORTED = -1, -3          # cv_status of include/cosyvoice_amd.h
+    t, r = _flowblock_blocks()
+    HEAD, TAIL, BOTH = ("cv_tblock_head",), ("cv_tblock_tail",), ("cv_tblock_tail_head",)
+    RES = ("cv_resblock_conv1", "cv_resblock_conv2")
+    cases = [   # (block, entry points, {field: bad value}, status)
+        (t, HEAD + BOTH, dict(ldqk=1028), ARG),                    # ldqk % 8: [Q | K] rows are written with 16-byte stores
+        (t, HEAD + BOTH, dict(vt_ld=18), ARG),                     # vt_ld % 4
+        (t, HEAD + BOTH, dict(T=17, vt_ld=16), ARG),               # vt_ld < T
+        (t, HEAD + BOTH, dict(qk=24), ARG),                        # qk not 16-byte aligned
+        (t, HEAD + TAIL + BOTH, dict(x=24), ARG),                  # x not 16-byte aligned
+        (t, HEAD + TAIL + BOTH, dict(ldx=258), ARG),               # ldx % 4
+        (t, BOTH, dict(out_act=16, ldoa=256), ARG),                # the 16-bit copy belongs to a block without a following head
+        (t, TAIL + BOTH, dict(wo_p=0), ARG),                       # ao without wo_p
+        (t, HEAD + BOTH, dict(T=1 << 20, vt_ld=1 << 20, ldqk=1024), ARG),   # T ldqk 2 = 2^31: past the 32-bit buffer offsets
+        (t, HEAD + TAIL + BOTH, dict(C=128), UNSUPPORTED), (t, HEAD + TAIL + BOTH, dict(inner=256), UNSUPPORTED),
+        (t, HEAD + TAIL + BOTH, dict(ff=2048), UNSUPPORTED), (t, HEAD + TAIL + BOTH, dict(dtype=L.CV_F32), UNSUPPORTED),
+        (r, RES, dict(cin=320, lda=312), ARG),                     # lda < cin
+        (r, RES, dict(lda=260), ARG),                              # lda % 8
+        (r, RES, dict(cin=384, lda=384), UNSUPPORTED), (r, RES, dict(dtype=L.CV_F32), UNSUPPORTED),
+    ]
+    for blk, entries, bad, status in cases:
+        saved = {f: getattr(blk, f) for f in bad}
+        for f, v in bad.items():
+            setattr(blk, f, v)
+        for e in entries:
+            assert getattr(lib, e)(ctypes.byref(blk), null) == status, (e, bad, status)
+        for f, v in saved.items():
+            setattr(blk, f, v)
+
+
 def test_csrc_reads_no_environment_variable():
     """Kernel variants are chosen by fields of a call's own parameter block: no source of the library calls getenv."""
     csrc = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "cosyvoice_amd", "csrc")
@@ -141,6 +195,7 @@ def test_version_and_unbound_entry_points_reject_null_arguments():
 # A new export fails test_every_export_has_a_test_module until somebody decides where it is tested.
 _HELPERS, _GRAPH = "test_helper_kernels_gpu", ("test_flow_gpu", "use_graph = True")
 _LLM_OPS = "test_llm_ops_gpu"
+_FLOWBLOCK = "test_flowblock_ops_gpu"
 COVERAGE = {
     "cv_version": "test_abi_cpu", "cv_arch": "test_abi_cpu",
     "cv_gemm": "test_gemm_modes_gpu", "cv_layernorm": "test_gemm_gpu", "cv_attention": "test_attention_ops_gpu",
@@ -157,11 +212,11 @@ COVERAGE = {
     "cv_stft_magnitude": _HELPERS, "cv_log_clamp_channels_first": _HELPERS,
     "cv_groupnorm_cl": "test_flow_v1_gpu", "cv_groupnorm_workspace_floats": ("test_flow_v1_gpu", "ops.groupnorm_workspace"),
     "cv_interp_linear_cl": _HELPERS, "cv_sizeof_groupnorm_params": "lifecycle", "cv_relpos_append": _HELPERS,
-    "cv_sizeof_tblock_params": "lifecycle", "cv_tblock_head": "test_tblock_gpu", "cv_tblock_tail": "test_tblock_gpu",
-    "cv_tblock_tail_head": "test_tblock_gpu",
+    "cv_sizeof_tblock_params": "lifecycle", "cv_tblock_head": _FLOWBLOCK, "cv_tblock_tail": _FLOWBLOCK,
+    "cv_tblock_tail_head": _FLOWBLOCK,
     "cv_sizeof_llm_step_desc": "lifecycle", "cv_sizeof_llm_layer": "lifecycle", "cv_llm_step_enqueue": "test_abi_cpu",
     "cv_llm_step_graph_create": "test_llm_gpu", "cv_llm_step_graph_launch": "test_abi_cpu", "cv_llm_step_graph_destroy": "lifecycle",
-    "cv_sizeof_resblock_params": "lifecycle", "cv_resblock_conv1": "test_tblock_gpu", "cv_resblock_conv2": "test_tblock_gpu",
+    "cv_sizeof_resblock_params": "lifecycle", "cv_resblock_conv1": _FLOWBLOCK, "cv_resblock_conv2": _FLOWBLOCK,
     "cv_sizeof_flow_solver_desc": "lifecycle", "cv_sizeof_flow_block": "lifecycle", "cv_sizeof_flow_tblock": "lifecycle",
     "cv_flow_euler_enqueue": "test_abi_cpu", "cv_flow_euler_graph_create": "test_tblock_gpu", "cv_flow_euler_graph_launch": "test_abi_cpu",
     "cv_flow_euler_graph_destroy": "lifecycle",
