@@ -13,7 +13,6 @@ Beyond the reference (which is batch-1 only, flow.py:277): ``inference_batch`` r
 one pass (the CFG pair of every utterance is batched: 2B sequences per estimator call).
 """
 import math
-import os
 from typing import Dict, List, Optional
 
 import torch
@@ -345,6 +344,9 @@ class ConditionalDecoder:
     def __init__(self, cfg: FlowConfig, dtype, device):
         self.cfg, self.dtype, self.device = cfg, dtype, device
         self.static_chunk_size = 0
+        self.use_fused = True          # row-block kernels where the widths allow (see ``fused``); False: A/B measurements, cross-check tests
+        self.use_fused_resnet = True   # ... for the resnet blocks too (see ``_fused_resnet``)
+        self.use_tail_head = True      # a block's tail and the next block's head as one launch (see ``fuse_tail_head``)
         self._ws: Dict[tuple, dict] = {}
         self._tcache: Dict[tuple, torch.Tensor] = {}
 
@@ -360,16 +362,19 @@ class ConditionalDecoder:
     def fused(self):
         """The row-block kernels (cv_tblock_head / cv_tblock_tail) cover the widths of the reference wiring (256 channels, 8 x 64
         heads, 4 x FFN: cosyvoice2 yaml :68-78) in 16-bit operands; anything else keeps the cv_gemm / cv_layernorm launches.
-        CV_FLOW_FUSED=0 forces the unfused launches (A/B measurements, cross-check tests)."""
+        ``use_fused = False`` forces the unfused launches."""
         cfg = self.cfg
-        return (os.environ.get("CV_FLOW_FUSED", "1") != "0" and self.dtype in (torch.float16, torch.bfloat16)
+        return (self.use_fused and self.dtype in (torch.float16, torch.bfloat16)
                 and cfg.est_channels == 256 and cfg.est_inner == 512 and cfg.est_head_dim == 64 and cfg.est_ff_mult == 4)
 
     @property
     def fused_all(self):
         """Every block runs on the row-block kernels (what cv_flow_euler_* composes): fused widths and packed resnet weights."""
-        return (self.fused and os.environ.get("CV_FLOW_FUSED_RESNET", "1") != "0"
-                and all("w1_p" in blk["res"] and blk["res"]["wr"].shape[1] in (256, 320, 512) for blk in self.blocks))
+        return all(self._fused_resnet(blk["res"], blk["res"]["wr"].shape[1]) for blk in self.blocks)
+
+    def _fused_resnet(self, rs, cin):
+        """This resnet block runs as the two row-block launches (cv_resblock_conv1 / conv2): packed weights, a covered input width."""
+        return bool(self.fused and self.use_fused_resnet and "w1_p" in rs and cin in (256, 320, 512))
 
     def _load_tblock(self, P, sd, name):
         wqk = torch.cat([sd[f"{name}.attn1.to_q.weight"].float(), sd[f"{name}.attn1.to_k.weight"].float()], 0)
@@ -467,7 +472,7 @@ class ConditionalDecoder:
     def _resnet(self, rs, ws, R, a_in, lda, cin, tadd):
         C, T = self.cfg.est_channels, ws["T"]
         rows = R * T
-        if "w1_p" in rs and self.fused and cin in (256, 320, 512) and os.environ.get("CV_FLOW_FUSED_RESNET", "1") != "0":
+        if self._fused_resnet(rs, cin):
             # two row-block launches: conv + LayerNorm + Mish + time term | conv + LayerNorm + Mish + 1x1 conv of the input
             p = L.ResblockParams()
             p.dtype, p.R, p.T, p.C, p.cin = L.TORCH_DT[self.dtype], R, T, C, cin
@@ -525,7 +530,7 @@ class ConditionalDecoder:
     @property
     def fuse_tail_head(self):
         """Blocks j < n_tb - 1 of a group run their tail together with the next block's head (one launch, x not re-read)."""
-        return bool(self.fused) and os.environ.get("CV_FLOW_FUSE_TAIL_HEAD", "1") != "0"
+        return bool(self.fused and self.use_tail_head)
 
     def _tblock_group(self, tbs, ws, R, klen, out_act=None, ldoa=0):
         """The n_tb transformer blocks behind one resnet block; the last one also leaves the 16-bit copy ``out_act``."""
@@ -635,7 +640,7 @@ class CausalConditionalCFM:
         self._noise_cl = self.rand_noise[0].t().contiguous().to(device)  # (15000, 80) channels-last
         self._graphs: Dict[tuple, tuple] = {}
         self.use_graph = False
-        self.use_stage_abi = os.environ.get("CV_FLOW_STAGE_ABI", "1") != "0"   # solver graph built by cv_flow_euler_graph_create
+        self.use_stage_abi = True   # solver graph built by cv_flow_euler_graph_create
 
     def schedule(self, n_timesteps):
         """t values fed to the estimator and the dt of every Euler step, with the reference's fp32 accumulation order
@@ -669,27 +674,21 @@ class CausalConditionalCFM:
                 klen2 = self._klen2[B] = torch.zeros(2 * B, device=x.device, dtype=torch.int32)
             klen2.copy_(klen.repeat_interleave(2))
 
-        def run():
+        def run():   # the eager path, and the cross-check of the library's own composition of the same launches (tests/test_flow_gpu.py)
             for i in range(n_timesteps):
                 ops.est_pack(x, mu, spks, cond, ws["xin"])
                 est.forward_cl(ws, R, tt[i], klen2)
                 ops.cfm_update(x, ws["v"], dts[i], self.inference_cfg_rate)
 
-        # stage-level ABI (cv_flow_euler_*): the library composes and captures the same launch sequence from a descriptor;
-        # `run` stays as the eager path and as the cross-check of the C composition (tests/test_flow_gpu.py)
-        stage_abi = self.use_stage_abi and getattr(est, "fused_all", False)   # (the v1 estimator, flow_v1.py, has no fused form)
-
         if not self.use_graph:
             run()
             return x
-        key = (B, T, n_timesteps, x.data_ptr(), mu.data_ptr(), spks.data_ptr(), cond.data_ptr(),
-               0 if klen2 is None else klen2.data_ptr(), int(getattr(est, "cu_budget", 0) or 0), est.fused, getattr(est, "fuse_tail_head", False))
-        key = key + (stage_abi,)
+        key = self._graph_key(x, mu, spks, cond, klen2, n_timesteps)
         g = self._graphs.get(key)
         if g is None:
             run()  # warm every lazily-built table outside capture
             torch.cuda.synchronize()
-            if stage_abi:
+            if self.stage_abi:
                 desc, keep = self.solver_desc(x, mu, spks, cond, klen2, ws, tt, dts)
                 g = ops.Graph.from_flow_solver(desc, keep)
             else:
@@ -698,6 +697,18 @@ class CausalConditionalCFM:
             return x  # the eager warm-up already produced the result (x was advanced once)
         g.launch()
         return x
+
+    @property
+    def stage_abi(self):
+        """The library composes and captures the solve from a descriptor (cv_flow_euler_*: the fused CosyVoice2 estimator only)."""
+        return bool(self.use_stage_abi and self.estimator.fused_all)
+
+    def _graph_key(self, x, mu, spks, cond, klen2, n_timesteps):
+        """Key of a captured solve: shape, the addresses baked into the graph, and every option that changes its launches."""
+        est = self.estimator
+        return (x.shape[0], x.shape[1], n_timesteps, x.data_ptr(), mu.data_ptr(), spks.data_ptr(), cond.data_ptr(),
+                0 if klen2 is None else klen2.data_ptr(), int(getattr(est, "cu_budget", 0) or 0), est.fused, est.fuse_tail_head,
+                est.use_fused_resnet, self.stage_abi)
 
     def solver_desc(self, x, mu, spks, cond, klen2, ws, tt, dts):
         """cv_flow_solver_desc of this solve (include/cosyvoice_amd.h) + the host arrays it points to."""
@@ -770,6 +781,7 @@ class CausalMaskedDiffWithXvec:
         self._loaded = False
         self._bufs: Dict[tuple, dict] = {}
         self._stream_caches: Dict[object, "EncoderStreamCache"] = {}   # cache_key of a streaming request -> its encoder cache
+        self.stream_enc_cache = True   # keep a streaming request's encoder state between its chunk calls (see ``inference``)
 
     def to(self, *a, **k):
         return self
@@ -922,7 +934,7 @@ class CausalMaskedDiffWithXvec:
                   flow_cache=None, sample_rate=24000, n_timesteps=10, begin=False, finalize=True, cache_key=None):
         """Reference signature (flow.py:260-272) -> (mel (1,80,T_g) float32, None).  ``cache_key`` (extra keyword, absent from the
         reference): identifies a streaming request across its chunk calls; its chunk-causal encoder state is then kept between the
-        calls (CV_STREAM_ENC_CACHE=0 turns that off: every call re-encodes everything, as the reference does)."""
+        calls (``stream_enc_cache = False`` turns that off: every call re-encodes everything, as the reference does)."""
         assert token.shape[0] == 1
         r = self.token_mel_ratio
         if int(prompt_feat_len[0]) % r != 0:  # flow.py:279-283 (mutates the length tensors in place, as the reference)
@@ -931,7 +943,7 @@ class CausalMaskedDiffWithXvec:
             prompt_token_len[0] = prompt_feat_len[0] // r
             prompt_token = prompt_token[:, :int(prompt_token_len[0])]
         ec = None
-        if cache_key is not None and os.environ.get("CV_STREAM_ENC_CACHE", "1") != "0" and int(self.encoder.static_chunk_size) > 0:
+        if cache_key is not None and self.stream_enc_cache and int(self.encoder.static_chunk_size) > 0:
             need = int(prompt_token.shape[1] + token.shape[1]) + 64
             ec = self._stream_caches.get(cache_key)
             if ec is None or ec.cap < need:     # first call of the request, or the request outgrew its cache: start over, larger

@@ -9,7 +9,6 @@ channels-last activations, every Conv1d / ConvTranspose1d as an implicit-GEMM MF
 the Snake / leaky-relu / residual / 1/3-mean fused into the epilogues.
 """
 import math
-import os
 from typing import Dict, List, Optional, Sequence
 
 import torch
@@ -89,7 +88,8 @@ class HiFTGenerator:
         self.num_upsamples = len(self.cfg.upsample_rates)
         self._loaded = False
         self._ws: Dict[tuple, dict] = {}
-        self.use_stage_abi = os.environ.get("CV_HIFT_STAGE_ABI", "1") != "0"   # decode composed by cv_hift_decode_enqueue
+        self.use_stage_abi = True   # decode composed by cv_hift_decode_enqueue
+        self.use_presplit = True    # pre-split fp32 activations / weights where the format allows (see ``presplit``)
         # ragged calls run at the longest utterance's frame count rounded up to this many frames (100 = 2 s of v2 audio): one workspace and
         # one descriptor per (B, T) serve every set of lengths <= T, so a service meets a handful of shapes.  The padding costs memory only —
         # the kernels skip the row tiles past an utterance's own length.
@@ -99,10 +99,10 @@ class HiFTGenerator:
     def presplit(self):
         """fp32 tensors with bf16x3 products: activations between the decoder's convs and the weights are kept PRE-SPLIT (hi / lo bf16
         planes per 4 values, cv_gemm_params.x3_flags) — the producer's epilogue splits once what every consuming conv would otherwise
-        split once per tap and tile column.  Bit-identical to the plain bf16x3 launches (CV_HIFT_PRESPLIT=0), tested."""
+        split once per tap and tile column.  Bit-identical to the plain bf16x3 launches (``use_presplit = False``), tested."""
         chans = [self.cfg.base_channels // 2 ** i for i in range(self.num_upsamples + 1)]   # 8-value groups along the channel axis
         return (self.dtype == torch.float32 and self.f32_products == "bf16x3" and all(c % 8 == 0 for c in chans)
-                and os.environ.get("CV_HIFT_PRESPLIT", "1") != "0")
+                and self.use_presplit)
 
     # -- torch.nn.Module-like surface used by cli/model.py:72-81
     def to(self, *a, **k):

@@ -15,7 +15,6 @@ Batching: B <= 16 sequences per step share every weight read (the reference is b
 """
 import copy
 import math
-import os
 from typing import Dict, Generator, List, Optional
 
 import torch
@@ -32,7 +31,7 @@ def _round_up(x, m):
 
 
 class Qwen2LM:
-    DOWN_KSPLIT = int(os.environ.get("CV_DOWN_KSPLIT", "4"))  # down-projection K slices (1: in-place `x +=`, no slabs)
+    DOWN_KSPLIT = 4   # down-projection K slices: every step sums that many split-K slabs into the residual
 
     def __init__(self, cfg: Optional[LlmConfig] = None, dtype: torch.dtype = torch.bfloat16, device: str = "cuda",
                  max_batch: int = 8, ctx_max: int = 1024, max_out: int = 2048, top_p: float = 0.8, top_k: int = 25,
@@ -54,9 +53,10 @@ class Qwen2LM:
         # group prefetched (cv_skinny_params.max_wgs).  Measured slower than single-shot workgroups at three per CU on the
         # 104-CU share tts_batches gives the decode loop (tools/llm_kernel_bench.py), so it stays off.
         self.cu_budget = 0
-        self.split_norm = os.environ.get("CV_SPLIT_NORM", "1") != "0"   # decode step: post-attention RMSNorm split over o_proj / gate-up
+        self.split_norm = True       # decode step: post-attention RMSNorm split over o_proj / gate-up
+        self.split_qkv_norm = None   # QKV RMSNorm as its own launch: None = when a step has more than 8 rows, True / False force it
         self.use_graph = True
-        self.use_stage_abi = os.environ.get("CV_LLM_STAGE_ABI", "1") != "0"   # decode-step graph built by cv_llm_step_graph_create
+        self.use_stage_abi = True    # decode-step graph built by cv_llm_step_graph_create
         self._loaded = False
         self._graphs: Dict[int, ops.Graph] = {}
         self._prefill_ws: Dict[tuple, dict] = {}
@@ -178,9 +178,8 @@ class Qwen2LM:
         return 16 if B <= 16 else 32
 
     def _split_qkv(self, B):
-        """QKV RMSNorm as its own launch (see _decode_step): CV_SPLIT_QKV_NORM=0/1 forces it, default = more than 8 rows."""
-        v = os.environ.get("CV_SPLIT_QKV_NORM")
-        return self.split_norm and self.DOWN_KSPLIT >= 2 and ((v == "1") if v in ("0", "1") else B > 8)
+        """QKV RMSNorm as its own launch (see _decode_step): ``split_qkv_norm`` True / False forces it, None = more than 8 rows."""
+        return self.split_norm and (B > 8 if self.split_qkv_norm is None else bool(self.split_qkv_norm))
 
     def _step_desc(self, B, use_forced, use_uniforms):
         """The decode step as ONE descriptor for the stage-level ABI (cv_llm_step_graph_create): every weight / state pointer of
@@ -225,23 +224,6 @@ class Qwen2LM:
         KS = self.DOWN_KSPLIT
         scale = 1.0 / math.sqrt(cfg.head_dim)
         mw = self.cu_budget
-        # residual stream ping-pongs between x (even layers) and x2 (odd): the fused prologue of the QKV kernel reads
-        # cur (+ the previous layer's down-proj slabs) and its workgroup (0,0) writes the summed residual to nxt
-        if KS == 1:
-            # the residual row is updated in place by the two `out +=` projections; every norm prologue reads it directly
-            x = st["x"]
-            for li, lay in enumerate(self.layers):
-                ops.skinny_gemm(st["xn"], lay["p_qkv"], B, qkv_dim, H, bias=lay["bqkv"], out_f32=st["qkv"], ldo=qkv_dim,
-                                norm=dict(x=x, gamma=lay["g_in"], eps=cfg.rms_eps))
-                ops.decode_attention(st["q"], self.kcache[li], self.vtcache[li], st["pos"], 1, st["ao"], B, cfg.num_heads,
-                                     cfg.num_kv_heads, self.ctx_max, scale, qkv=st["qkv"], inv_freq=self.rope_table)
-                ops.skinny_gemm(st["ao"], lay["p_o"], B, H, cfg.q_dim, mode=1, out_f32=x, ldo=H)
-                ops.skinny_gemm(st["xn"], lay["p_gu"], B, 2 * I, H, mode=2, out_act=st["h"], ldoa=I,
-                                norm=dict(x=x, gamma=lay["g_post"], eps=cfg.rms_eps))
-                ops.skinny_gemm(st["h"], lay["p_down"], B, H, I, mode=1, out_f32=x, ldo=H)
-            ops.rmsnorm_reduce(x, self.g_final, cfg.rms_eps, st["xn"], B)
-            self._head_and_sample(B, use_forced, use_uniforms)
-            return
         if self._split_qkv(B):
             # more than 8 rows: the QKV kernel's fused prologue (each of its 72 workgroups re-reads the fp32 residual + KS slabs of
             # every row: 286 KB at 16 rows) costs more than a launch — one workgroup per row sums the slabs into the residual and
@@ -264,6 +246,8 @@ class Qwen2LM:
             ops.rmsnorm_reduce(x, self.g_final, cfg.rms_eps, st["xn"], B, slabs=st["slabs"], nslab=KS, slab_stride=self._rp(B) * H, ld_slab=H)
             self._head_and_sample(B, use_forced, use_uniforms)
             return
+        # residual stream ping-pongs between x (even layers) and x2 (odd): the fused prologue of the QKV kernel reads
+        # cur (+ the previous layer's down-proj slabs) and its workgroup (0,0) writes the summed residual to nxt
         cur, nxt = st["x"], st["x2"]
         for li, lay in enumerate(self.layers):
             nrm = dict(x=cur, gamma=lay["g_in"], eps=cfg.rms_eps, x_out=nxt)
@@ -289,15 +273,19 @@ class Qwen2LM:
         ops.rmsnorm_reduce(cur, self.g_final, cfg.rms_eps, st["xn"], B, slabs=st["slabs"], nslab=KS, slab_stride=self._rp(B) * H, ld_slab=H)
         self._head_and_sample(B, use_forced, use_uniforms)
 
+    def _graph_key(self, B, use_forced, use_uniforms):
+        """Key of a captured step: the launch shape plus every option that changes the step's launches or their arguments."""
+        return (B, use_forced, use_uniforms, self.seed, self.cu_budget, self.top_p, self.top_k, self.fallback_mode, self.top_p2, self.top_k2,
+                self.split_norm, self.use_stage_abi, bool(self._split_qkv(B)))
+
     def _step(self, B, use_forced, use_uniforms):
         if not self.use_graph:
             self._decode_step(B, use_forced, use_uniforms)
             return
-        key = (B, use_forced, use_uniforms, self.seed, self.cu_budget, self.top_p, self.top_k, self.fallback_mode, self.top_p2, self.top_k2,
-               self.split_norm, self.use_stage_abi)
+        key = self._graph_key(B, use_forced, use_uniforms)
         g = self._graphs.get(key)
         if g is None:
-            if self.use_stage_abi and self.split_norm and self.DOWN_KSPLIT >= 2 and self.cu_budget == 0:
+            if self.use_stage_abi and self.split_norm and self.cu_budget == 0:
                 # the whole step composed and captured inside the library (cv_llm_step_graph_create): same launches as
                 # _decode_step, which stays as the eager path and as the cross-check of the C composition (tests)
                 g = ops.Graph.from_llm_step(self._step_desc(B, use_forced, use_uniforms))

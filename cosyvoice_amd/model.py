@@ -9,7 +9,6 @@ The stage objects are the HIP-backed ``cosyvoice_amd.llm.Qwen2LM`` / ``flow.Caus
 ``tts_batch`` is the build's utterance-batched entry (the reference is batch-1): LLM decode batched over B
 sequences, flow batched over B CFG pairs, HiFT batched over B mels.
 """
-import os
 import collections
 import threading
 import time
@@ -64,7 +63,7 @@ class CosyVoice2Model:
         self.llm_loops = 2      # tts_batches: concurrent decode loops (each its own batch / KV caches) on those CUs
         self.llm_merge = 1      # tts_batches: consecutive batches decoded by ONE token loop (rows <= llm.max_batch)
         self.flow_merge = 1     # tts_batches: up to this many consecutive batches whose tokens are ready share ONE flow + HiFT pass
-        self.llm_ramp = (1, 2, 2, 3)   # tts_batches: batches per decode job while the pipeline fills (then llm_merge); CV_LLM_RAMP overrides
+        self.llm_ramp = (1, 2, 2, 3)   # tts_batches: batches per decode job while the pipeline fills (then llm_merge)
         self.lock = threading.Lock()
         # The reference's modules are re-entrant (every call builds its own activations / KV cache) and it interleaves requests:
         # one LLM thread + side stream per tts() call (cli/model.py:62,119,189).  Here a decode loop owns KV caches, device state and
@@ -83,11 +82,11 @@ class CosyVoice2Model:
         self.hift_cache_dict = {}
         self._llm_spans = collections.OrderedDict()   # uuid -> [start, end] wall-clock of the request's token loop (diagnostics / tests); the last 64 requests
         self._llm_errors = {}     # uuid -> exception raised inside the request's LLM thread; tts() re-raises it in the caller
-        self.overlap_hift = os.environ.get("CV_OVERLAP_HIFT", "0") != "0"   # tts_batches: HiFT of batch i on its own stream beside flow of batch i + 1 (measured SLOWER: 455 vs 548 audio-s/s — the vocoder GEMMs and the flow chain disturb each other on shared CUs; kept for experiments)
+        self.overlap_hift = False   # tts_batches: HiFT of batch i on its own stream beside flow of batch i + 1 (measured SLOWER: 455 vs 548 audio-s/s — the vocoder GEMMs and the flow chain disturb each other on shared CUs; kept for experiments)
         # tts_batches: where the decode jobs' prefills run.  True = on the flow CUs (throughput-bound GEMM work over B x 282 rows); False = on
         # the decode CUs with the token loop.  Re-checked in round 2, when the flow + HiFT stream became the bottleneck: still better on the
         # flow CUs (622-631 vs 605-612 audio-s/s) — on 64 CUs a 32-row prefill stalls both token loops for ~0.1 s per job
-        self.prefill_on_flow_cus = os.environ.get("CV_PREFILL_ON_FLOW", "1") != "0"
+        self.prefill_on_flow_cus = True
         self.pipeline_stats = None  # set to a list to collect (stage, batches, start, end) of every tts_batches job
         # utterances of different generated lengths (free-running sampling): True = ONE ragged vocoder pass over the padded batch
         # (HiFTGenerator.inference_ragged, exact per utterance); False = the per-utterance loop of batch-1 vocoder calls, kept as the cross-check
@@ -664,7 +663,7 @@ class CosyVoice2Model:
         llm_state = {"running": 0, "all_submitted": False}
         # pipeline fill: the first decode jobs are small so that the flow stream gets its first batches early and is then fed without a
         # gap while the job size grows to `merge` (1, 2, 2, 3, merge, ...: with 4 batches per job from the start the flow CUs idled ~0.2 s)
-        ramp = [int(v) for v in os.environ.get("CV_LLM_RAMP", ",".join(str(v) for v in self.llm_ramp)).split(",") if v]
+        ramp = [int(v) for v in self.llm_ramp]
         n_jobs = 0
         with ThreadPoolExecutor(max_workers=n_llm) as llm_pool, ThreadPoolExecutor(max_workers=1) as flow_pool, \
                 ThreadPoolExecutor(max_workers=1) as hift_pool:

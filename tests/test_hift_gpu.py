@@ -143,7 +143,7 @@ def test_stage_abi_decode_equals_python_composed_decode(tag, dt, mode):
 
 
 @pytest.mark.parametrize("tag", ["tiny", "v2"])
-def test_presplit_storage_is_bit_identical(tag, monkeypatch):
+def test_presplit_storage_is_bit_identical(tag):
     """bf16x3 decoder convs with PRE-SPLIT activation / weight storage (hi / lo bf16 planes per 4 values, written once by the producing
     epilogue) against the plain bf16x3 launches that split every operand tile as it is staged: same hi / lo bits, same MFMAs — bit-identical
     on the implicit-GEMM kernel (the default).  The opt-in activation-window kernel (conv_win=1) sums chunk-major (64 channels at a time,
@@ -157,8 +157,9 @@ def test_presplit_storage_is_bit_identical(tag, monkeypatch):
     s = (torch.randn(B, 1, T * cfg.total_upsample) * 0.05).cuda()
     outs = {}
     for flag, win in (("1", "0"), ("0", "0"), ("1", "1")):
-        monkeypatch.setenv("CV_HIFT_PRESPLIT", flag)
-        m = HiFTGenerator(cfg, dtype=torch.float32, f32_products="bf16x3", conv_win=int(win)).load_state_dict(sd)
+        m = HiFTGenerator(cfg, dtype=torch.float32, f32_products="bf16x3", conv_win=int(win))
+        m.use_presplit = flag == "1"
+        m.load_state_dict(sd)
         assert m.presplit == (flag == "1")
         outs[flag + win] = m.decode(mel, s).clone()
     torch.cuda.synchronize()

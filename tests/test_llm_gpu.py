@@ -425,7 +425,7 @@ def test_generate_from_ready_made_prefill_embeddings():
 
 
 @pytest.mark.parametrize("split_qkv", ["0", "1"])
-def test_stage_abi_step_equals_python_composed_step(split_qkv, monkeypatch):
+def test_stage_abi_step_equals_python_composed_step(split_qkv):
     """(both forms of the input RMSNorm: fused into the QKV kernel's prologue / its own cv_rmsnorm_reduce launch, the >8-row default)
     cv_llm_step_graph_create (the decode step composed + captured inside the library) against the same step composed launch by
     launch from Python: teacher-forced logits and free-running tokens (injected uniforms) bit-identical; the header's stage entry
@@ -439,11 +439,11 @@ def test_stage_abi_step_equals_python_composed_step(split_qkv, monkeypatch):
     ps = torch.randint(0, cfg.speech_token_size, (1, 8), generator=g, dtype=torch.int32)
     forced = torch.randint(0, cfg.speech_token_size, (9,), generator=g).tolist()
     uni = torch.rand(16, 101, 2, generator=g) * 0.98
-    monkeypatch.setenv("CV_SPLIT_QKV_NORM", split_qkv)
     outs = {}
     for abi in (True, False):
         lm = Qwen2LM(cfg, dtype=torch.bfloat16, max_batch=4, ctx_max=256, max_out=256)
         lm.use_stage_abi = abi
+        lm.split_qkv_norm = split_qkv == "1"
         lm.load_state_dict(sd)
         lp = lm.forced_logits(text, ptext, ps, forced).cpu()
         toks = lm.generate_batch([text, text], [ptext, ptext], [ps, ps[:, :5]], uniforms=uni, max_steps=40)
@@ -451,6 +451,33 @@ def test_stage_abi_step_equals_python_composed_step(split_qkv, monkeypatch):
     assert torch.equal(outs[True][0], outs[False][0])
     assert outs[True][1] == outs[False][1] and all(len(t) >= 10 for t in outs[True][1])
     assert outs[True][2] >= 1
+
+
+def test_split_qkv_norm_toggled_between_calls_on_one_object():
+    """``split_qkv_norm`` is part of the step graph's key: changed between calls on one object (captured steps), every call runs the
+    step of the setting it was made under — bit-identical to a fresh model constructed with that setting — and the second setting
+    captures graphs of its own instead of replaying the first one's."""
+    from cosyvoice_amd.llm import Qwen2LM
+    cfg = LlmConfig.tiny()
+    sd = llm_state_dict(cfg)
+    g = torch.Generator().manual_seed(3)
+    text = torch.randint(0, cfg.vocab_size, (1, 6), generator=g, dtype=torch.int32)
+    ptext = torch.randint(0, cfg.vocab_size, (1, 3), generator=g, dtype=torch.int32)
+    ps = torch.randint(0, cfg.speech_token_size, (1, 8), generator=g, dtype=torch.int32)
+    forced = torch.randint(0, cfg.speech_token_size, (9,), generator=g).tolist()
+    fresh = {}
+    for v in (False, True):
+        m = Qwen2LM(cfg, max_batch=4, ctx_max=256, max_out=256)
+        m.split_qkv_norm = v
+        fresh[v] = m.load_state_dict(sd).forced_logits(text, ptext, ps, forced).cpu()
+    lm = Qwen2LM(cfg, max_batch=4, ctx_max=256, max_out=256).load_state_dict(sd)
+    assert lm.use_graph
+    n_graphs = []
+    for v in (False, True, False):
+        lm.split_qkv_norm = v
+        assert torch.equal(lm.forced_logits(text, ptext, ps, forced).cpu(), fresh[v]), v
+        n_graphs.append(len(lm._graphs))
+    assert n_graphs[0] >= 1 and n_graphs[1] > n_graphs[0] and n_graphs[2] == n_graphs[1]
 
 
 def test_32_row_token_loop_equals_two_16_row_loops():

@@ -56,7 +56,7 @@ def test_cached_encoder_equals_full_pass(dt, tol, bucket):
     assert encoded == exp, (encoded, exp)
 
 
-def test_streaming_mel_with_encoder_cache_equals_recompute(monkeypatch):
+def test_streaming_mel_with_encoder_cache_equals_recompute():
     """Full-depth flow, the C4 prompt (250 tokens) and the streaming schedule of cli/model.py:380-407 (hop 50 + 3 look-ahead, then the
     tail): every chunk's mel with the encoder cache == without it, and the cache re-encodes 53-ish rows per chunk instead of 300+."""
     from cosyvoice_amd.flow import CausalMaskedDiffWithXvec
@@ -93,6 +93,6 @@ def test_streaming_mel_with_encoder_cache_equals_recompute(monkeypatch):
     assert ec.calls == 4 and ec.rows_encoded == 325 + 75 + 75 + 25
     flow.drop_stream_cache("req-1")
     assert "req-1" not in flow._stream_caches
-    monkeypatch.setenv("CV_STREAM_ENC_CACHE", "0")
+    flow.stream_enc_cache = False
     off = run("req-2")
     assert "req-2" not in flow._stream_caches and all(torch.equal(a, b) for a, b in zip(off, ref))

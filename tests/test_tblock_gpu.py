@@ -177,8 +177,8 @@ def test_gelu_erf_polynomial():
 
 
 @pytest.mark.parametrize("dt,tol", [(torch.float16, 6e-3), (torch.bfloat16, 5e-2)])
-def test_fused_estimator_equals_unfused(dt, tol, monkeypatch):
-    """ConditionalDecoder.forward_cl with the row-block kernels vs the cv_gemm / cv_layernorm launches (CV_FLOW_FUSED=0) on the
+def test_fused_estimator_equals_unfused(dt, tol):
+    """ConditionalDecoder.forward_cl with the row-block kernels vs the cv_gemm / cv_layernorm launches (use_fused = False) on the
     same weights and inputs, tiny depth, T not a multiple of 64, batch of 2 CFG pairs."""
     from cosyvoice_amd.config import FlowConfig
     from cosyvoice_amd.flow import CausalMaskedDiffWithXvec
@@ -193,7 +193,7 @@ def test_fused_estimator_equals_unfused(dt, tol, monkeypatch):
     tt = est.time_table([0.3])
     outs = []
     for flag in ("1", "0"):
-        monkeypatch.setenv("CV_FLOW_FUSED", flag)
+        est.use_fused = flag == "1"
         ws = est._workspace(R, T)
         ws["xin"].copy_(xin)
         outs.append(est.forward_cl(ws, R, tt[0]).clone())
@@ -204,7 +204,7 @@ def test_fused_estimator_equals_unfused(dt, tol, monkeypatch):
 
 
 @pytest.mark.parametrize("dt,tol", [(torch.float16, 6e-3), (torch.bfloat16, 5e-2)])
-def test_estimator_tail_head_fusion_on_off(dt, tol, monkeypatch):
+def test_estimator_tail_head_fusion_on_off(dt, tol):
     """The estimator with cv_tblock_tail_head launches (default) against the three-launches-per-block composition, eager and through
     the stage ABI's captured solver: same kernels otherwise, LayerNorm statistics summed in a different order."""
     from cosyvoice_amd.config import FlowConfig
@@ -219,7 +219,7 @@ def test_estimator_tail_head_fusion_on_off(dt, tol, monkeypatch):
     tt = est.time_table([0.3])
     outs = []
     for flag in ("1", "0"):
-        monkeypatch.setenv("CV_FLOW_FUSE_TAIL_HEAD", flag)
+        est.use_tail_head = flag == "1"
         assert est.fuse_tail_head == (flag == "1")
         ws = est._workspace(R, T)
         ws["xin"].copy_(xin)
@@ -229,7 +229,7 @@ def test_estimator_tail_head_fusion_on_off(dt, tol, monkeypatch):
     print(f"estimator tail+head fusion on vs off [{dt}]: Linf {d.max().item():.3e} (values ~ {outs[1].abs().mean().item():.2f})")
     assert torch.isfinite(outs[0]).all() and d.max().item() < tol * max(1.0, outs[1].abs().max().item())
     # whole flow: eager composition == captured stage-ABI solver, with the fusion on
-    monkeypatch.setenv("CV_FLOW_FUSE_TAIL_HEAD", "1")
+    est.use_tail_head = True
     tok = torch.randint(0, cfg.vocab_size, (2, 14), generator=g, dtype=torch.int32)
     ptok = torch.randint(0, cfg.vocab_size, (2, 6), generator=g, dtype=torch.int32)
     pfeat = torch.clamp(torch.randn(2, 12, 80, generator=g) * 2 - 6, -11.5, 2.0)
@@ -240,6 +240,35 @@ def test_estimator_tail_head_fusion_on_off(dt, tol, monkeypatch):
     flow.inference_batch(tok, ptok, pfeat, emb)
     m_graph = flow.inference_batch(tok, ptok, pfeat, emb).clone()
     assert torch.equal(m_eager, m_graph)
+
+
+@pytest.mark.parametrize("dt", [torch.float16, torch.bfloat16])
+def test_fused_resnet_toggled_between_captured_solves(dt):
+    """``use_fused_resnet`` is part of the solver graph's key: changed between calls on one flow object with captured solvers, every
+    call (the one that captures and the replay) gives exactly the eager result of the setting it was made under."""
+    from cosyvoice_amd.config import FlowConfig
+    from cosyvoice_amd.flow import CausalMaskedDiffWithXvec
+    from cosyvoice_amd.weights import flow_state_dict
+    cfg = FlowConfig.tiny()
+    flow = CausalMaskedDiffWithXvec(cfg, dtype=dt).load_state_dict(flow_state_dict(cfg))
+    est = flow.decoder.estimator
+    g = torch.Generator().manual_seed(0)
+    tok = torch.randint(0, cfg.vocab_size, (2, 14), generator=g, dtype=torch.int32)
+    ptok = torch.randint(0, cfg.vocab_size, (2, 6), generator=g, dtype=torch.int32)
+    pfeat = torch.clamp(torch.randn(2, 12, 80, generator=g) * 2 - 6, -11.5, 2.0)
+    emb = torch.randn(2, cfg.spk_embed_dim, generator=g)
+    eager = {}
+    flow.decoder.use_graph = False
+    for v in (True, False):
+        est.use_fused_resnet = v
+        assert est.fused_all == v
+        eager[v] = flow.inference_batch(tok, ptok, pfeat, emb).clone()
+    flow.decoder.use_graph = True
+    for v in (True, False, True):
+        est.use_fused_resnet = v
+        for call in ("first", "replay"):
+            assert torch.equal(flow.inference_batch(tok, ptok, pfeat, emb), eager[v]), (v, call)
+    assert torch.isfinite(eager[True]).all() and len(flow.decoder._graphs) == 2
 
 
 @pytest.mark.parametrize("dt,tol", [(torch.float16, 6e-3), (torch.bfloat16, 5e-2)])

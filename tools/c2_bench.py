@@ -1,6 +1,7 @@
 """BASELINE config C2 / batch-1 flow: ONE utterance through the flow stage (encoder + 10 CFG Euler steps as one hipGraph), at
 T = 500 (250 tokens, no prompt: C2), T = 650 (C1: 75-token prompt + 250) and T = 1000 (C4's utterance: 250 + 250), all CUs, with the
-library's own tile choices.  Prints ms and TFLOP/s on SURVEY.md §8d's flop counts."""
+library's own tile choices.  Prints ms and TFLOP/s on SURVEY.md §8d's flop counts.  ``--unfused``, ``--unfused-resnet`` and
+``--no-tail-head`` clear the estimator's use_fused / use_fused_resnet / use_tail_head."""
 import os, sys, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from cosyvoice_amd.config import FlowConfig
@@ -9,7 +10,12 @@ from cosyvoice_amd.weights import flow_state_dict
 
 dt = torch.float16
 fc = FlowConfig.full()
-flow = CausalMaskedDiffWithXvec(fc, dtype=dt).load_state_dict(flow_state_dict(fc))
+flags = set(sys.argv[1:])
+assert flags <= {"--unfused", "--unfused-resnet", "--no-tail-head"}, flags
+flow = CausalMaskedDiffWithXvec(fc, dtype=dt)
+est = flow.decoder.estimator
+est.use_fused, est.use_fused_resnet, est.use_tail_head = "--unfused" not in flags, "--unfused-resnet" not in flags, "--no-tail-head" not in flags
+flow.load_state_dict(flow_state_dict(fc))
 flow.decoder.use_graph = True
 g = torch.Generator().manual_seed(3)
 dev = "cuda"

@@ -1,6 +1,7 @@
 """The bench's flow + HiFT stage alone (batch 8, 10 s prompt + 10 s generated: T = 1000, encoder + 10 CFG Euler steps captured as
 one hipGraph, then the vocoder) on all CUs, un-profiled: ms per batch and TFLOP/s on the estimator's 4.937 TF per utterance
-(SURVEY.md §8d).  CV_FLOW_FUSED=0 times the unfused cv_gemm / cv_layernorm launches for comparison."""
+(SURVEY.md §8d).  ``--unfused`` times the unfused cv_gemm / cv_layernorm launches for comparison (estimator.use_fused = False),
+``--no-presplit`` the vocoder's plain bf16x3 launches (hift.use_presplit = False)."""
 import os, sys, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench as B
@@ -9,12 +10,19 @@ from cosyvoice_amd.flow import CausalMaskedDiffWithXvec
 from cosyvoice_amd.hift import HiFTGenerator
 from cosyvoice_amd.weights import flow_state_dict, hift_state_dict
 
-dt = torch.float16 if (len(sys.argv) < 2 or sys.argv[1] == "fp16") else torch.bfloat16
-Bn = int(sys.argv[2]) if len(sys.argv) > 2 else 8
+flags = {a for a in sys.argv[1:] if a.startswith("--")}
+assert flags <= {"--unfused", "--no-presplit"}, flags
+pos = [a for a in sys.argv[1:] if not a.startswith("--")]
+dt = torch.float16 if (len(pos) < 1 or pos[0] == "fp16") else torch.bfloat16
+Bn = int(pos[1]) if len(pos) > 1 else 8
 lc, fc, hc = LlmConfig.full(), FlowConfig.full(), HiftConfig.v2()
-flow = CausalMaskedDiffWithXvec(fc, dtype=dt).load_state_dict(flow_state_dict(fc))
+flow = CausalMaskedDiffWithXvec(fc, dtype=dt)
+flow.decoder.estimator.use_fused = "--unfused" not in flags
+flow.load_state_dict(flow_state_dict(fc))
 flow.decoder.use_graph = True
-hift = HiFTGenerator(hc, dtype=torch.float32).load_state_dict(hift_state_dict(hc))
+hift = HiFTGenerator(hc, dtype=torch.float32)
+hift.use_presplit = "--no-presplit" not in flags
+hift.load_state_dict(hift_state_dict(hc))
 texts, forced, ptext, pspeech, pfeat, emb = B.make_inputs(lc, fc, 100)
 dev = "cuda"
 tok = torch.tensor(forced, dtype=torch.int32, device=dev)[:Bn]
