@@ -52,8 +52,8 @@ class ConditioningRing:
     broadcast (``on_start``) until its last consumer has finished (``on_done``, called by CosyVoice2Model.tts_batches once the
     batch's waveform has been collected: its decode, flow and vocoder jobs are complete), so the broadcast of a later batch can never
     rewrite conditioning a running flow / LLM job still reads.  The reference keeps such state per request uuid for the same reason
-    (cli/model.py:183-188,374-377).  ``acquire`` raises when every slot is taken: size the ring for the pipeline depth
-    (``tts_batches`` admits at most (llm_loops + 2) * llm_merge + llm_merge - 1 batches at once, plus one looked ahead).
+    (cli/model.py:183-188,374-377).  ``acquire`` raises when every slot is taken: size the ring for the pipeline depth,
+    ``CosyVoice2Model.tts_batches_depth()`` (on the CU partition (llm_loops + 2) * llm_merge batches in flight plus one looked ahead).
 
     A slot = the flat fp32 payload buffer (what the collective moves) + int32 tensors for the two token fields.  ``tensors(slot)``
     hands out (prompt mel view, embedding view, prompt speech tokens, prompt text ids); the views alias the payload, the token

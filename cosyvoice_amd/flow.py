@@ -347,6 +347,7 @@ class ConditionalDecoder:
         self.use_fused = True          # row-block kernels where the widths allow (see ``fused``); False: A/B measurements, cross-check tests
         self.use_fused_resnet = True   # ... for the resnet blocks too (see ``_fused_resnet``)
         self.use_tail_head = True      # a block's tail and the next block's head as one launch (see ``fuse_tail_head``)
+        self.cu_budget = 0             # CUs of the stream the launches go to (0 = all; set by the batch pipeline): tile-size choice only
         self._ws: Dict[tuple, dict] = {}
         self._tcache: Dict[tuple, torch.Tensor] = {}
 
@@ -482,7 +483,7 @@ class ConditionalDecoder:
             p.w2_p, p.b2, p.g2, p.be2 = rs["w2_p"].data_ptr(), rs["b2"].data_ptr(), rs["g2"].data_ptr(), rs["be2"].data_ptr()
             p.wr_p, p.br = rs["wr_p"].data_ptr(), rs["br"].data_ptr()
             p.out, p.ldo, p.eps = ws["x32"].data_ptr(), C, 1e-5
-            p.cus = int(getattr(self, "cu_budget", 0) or 0)
+            p.cus = self.cu_budget
             ops._issue("cv_resblock_conv1", p)
             ops._issue("cv_resblock_conv2", p)
             return
@@ -502,7 +503,7 @@ class ConditionalDecoder:
         """cv_tblock_params with the HEAD fields of ``tb`` filled in."""
         inner = self.cfg.est_inner
         p = ops.tblock_params(ws["x32"], R, ws["T"], 1e-5, self.dtype)
-        p.cus = int(getattr(self, "cu_budget", 0) or 0)   # CUs of the stream these launches go to (0 = all): tile-size choice only
+        p.cus = self.cu_budget   # CUs of the stream these launches go to (0 = all): tile-size choice only
         p.g1, p.b1n, p.wqkv_p = tb["g1"].data_ptr(), tb["b1"].data_ptr(), tb["wqkv_p"].data_ptr()
         p.qk, p.ldqk, p.vt, p.vt_ld = ws["qk"].data_ptr(), 2 * inner, ws["vt"].data_ptr(), ws["Tp"]
         return p
@@ -707,7 +708,7 @@ class CausalConditionalCFM:
         """Key of a captured solve: shape, the addresses baked into the graph, and every option that changes its launches."""
         est = self.estimator
         return (x.shape[0], x.shape[1], n_timesteps, x.data_ptr(), mu.data_ptr(), spks.data_ptr(), cond.data_ptr(),
-                0 if klen2 is None else klen2.data_ptr(), int(getattr(est, "cu_budget", 0) or 0), est.fused, est.fuse_tail_head,
+                0 if klen2 is None else klen2.data_ptr(), est.cu_budget, est.fused, est.fuse_tail_head,
                 est.use_fused_resnet, self.stage_abi)
 
     def solver_desc(self, x, mu, spks, cond, klen2, ws, tt, dts):
@@ -720,7 +721,7 @@ class CausalConditionalCFM:
         d.dtype, d.B, d.T, d.Tp = L.TORCH_DT[est.dtype], B, T, ws["Tp"]
         d.C, d.inner, d.ff, d.heads = cfg.est_channels, cfg.est_inner, cfg.est_channels * cfg.est_ff_mult, cfg.est_heads
         d.in_ch, d.out_ch = cfg.est_in_channels, cfg.output_size
-        d.n_blocks, d.n_steps, d.cus = len(est.blocks), len(dts), int(getattr(est, "cu_budget", 0) or 0)
+        d.n_blocks, d.n_steps, d.cus = len(est.blocks), len(dts), est.cu_budget
         d.cfg_rate, d.eps = self.inference_cfg_rate, 1e-5
         blocks = (L.FlowBlock * len(est.blocks))()
         keep = [blocks]

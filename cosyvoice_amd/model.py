@@ -19,6 +19,9 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from . import pipeline
+from .pipeline import CuPartition, ragged_prompts
+
 
 def fade_in_out(fade_in_mel, fade_out_mel, window):
     """utils/common.py:149-157 (host-side cross-fade of the stream seam)."""
@@ -28,11 +31,6 @@ def fade_in_out(fade_in_mel, fade_out_mel, window):
     w = torch.as_tensor(window)   # float64 hamming window, as the reference's numpy broadcast (result is cast back on assignment)
     fade_in_mel[..., :n] = fade_in_mel[..., :n] * w[:n] + fade_out_mel[..., -n:] * w[n:]
     return fade_in_mel.to(device)
-
-
-def _ragged_prompts(b):
-    """A batch whose flow prompts are per-utterance lists (different lengths) instead of stacked (B, Np) / (B, Tp, 80) tensors."""
-    return isinstance(b["flow_prompt_speech_tokens"], (list, tuple))
 
 
 class CosyVoice2Model:
@@ -294,7 +292,7 @@ class CosyVoice2Model:
         return wav.cpu() if to_host else wav.clone()   # never hand out a view of HiFT's per-shape workspace
 
     def cu_partition(self, llm_cu_slots: int, n_llm: int = 1):
-        """(llm_streams, flow_stream): CU-masked streams giving the decode loop(s) ``llm_cu_slots`` of the 32 CUs of every XCD
+        """``pipeline.CuPartition``: CU-masked streams giving the decode loop(s) ``llm_cu_slots`` of the 32 CUs of every XCD
         (one stream per concurrent decode loop, all on the same CUs) and flow + HiFT the rest (cached).  With both stages
         free to use all 256 CUs the decode step's short dependent kernels queue behind — and share CUs with — the flow
         GEMMs and run 1.6x slower while the two overlap (226 -> 368 ms per batch, tools/cumask_probe2.py); on disjoint CU
@@ -304,11 +302,9 @@ class CosyVoice2Model:
         if getattr(self, "_cu_partition_key", None) != key:
             self._release_partition()   # the previous split's streams are destroyed, not leaked
             k = llm_cu_slots
-            self._cu_partition = ([ops.masked_stream(lambda s, x: s < k) for _ in range(n_llm)],
-                                  ops.masked_stream(lambda s, x: s >= k),
-                                  ops.masked_stream(lambda s, x: s >= k),   # a decode loop borrowing the idle flow CUs
-                                  [ops.masked_stream(lambda s, x: s >= k) for _ in range(n_llm)],  # prefills, on the flow CUs
-                                  ops.masked_stream(lambda s, x: s >= k))   # HiFT of batch i beside the flow of batch i + 1
+            flow_cus = lambda: ops.masked_stream(lambda s, x: s >= k)
+            self._cu_partition = CuPartition(llm=[ops.masked_stream(lambda s, x: s < k) for _ in range(n_llm)], flow=flow_cus(),
+                                             borrow=flow_cus(), prefill=[flow_cus() for _ in range(n_llm)], hift=flow_cus())
             self._cu_partition_key = key
         return self._cu_partition
 
@@ -317,9 +313,9 @@ class CosyVoice2Model:
         part = getattr(self, "_cu_partition", None)
         if part is not None:
             torch.cuda.synchronize()
-            flat = list(part[0]) + [part[1], part[2]] + list(part[3]) + list(part[4:5])
-            for st in flat:
-                ops.destroy_masked_stream(st)
+            for field in part:
+                for st in (field if isinstance(field, list) else [field]):
+                    ops.destroy_masked_stream(st)
         self._cu_partition, self._cu_partition_key = None, None
 
     def close(self):
@@ -357,10 +353,10 @@ class CosyVoice2Model:
         n_llm = max(1, self.llm_loops if llm_loops is None else llm_loops)
         if not k:
             return
-        llm_parts, flow_part, _, prefill_parts, hift_part = self.cu_partition(k, n_llm)
+        part = self.cu_partition(k, n_llm)
         B = len(b["texts"])
         forced = b.get("forced")
-        for ctx, st, pf in zip(self.llm_contexts(n_llm), llm_parts, prefill_parts):
+        for ctx, st, pf in zip(self.llm_contexts(n_llm), part.llm, part.prefill):
             for j in range(1, max(1, int(self.llm_merge)) + 1):
                 if j * B > self.llm.max_batch:
                     break
@@ -368,12 +364,11 @@ class CosyVoice2Model:
                     ctx.generate_batch(b["texts"] * j, b["prompt_texts"] * j, b["llm_prompt_speech_tokens"] * j,
                                        forced=None if forced is None else [list(t) for t in forced] * j, steps_per_poll=64, max_steps=2,
                                        prefill_stream=pf if self.prefill_on_flow_cus else None)
-        est = getattr(getattr(self.flow, "decoder", None), "estimator", None)
+        est = self.flow.decoder.estimator
         flow_full = torch.cuda.Stream(self.device)
         zero = torch.zeros(1, 1, 0)
-        for budget, stream in (((32 - k) * 8, flow_part), (0, flow_full)):
-            if est is not None:
-                est.cu_budget = budget
+        for budget, stream in (((32 - k) * 8, part.flow), (0, flow_full)):
+            est.cu_budget = budget
             for j in range(1, max(1, int(self.flow_merge)) + 1):
                 rep = lambda t: torch.cat([t] * j, dim=0)
                 tok = torch.randint(0, self.flow.cfg.vocab_size, (j * B, n_tokens), dtype=torch.int32).to(self.device)
@@ -381,11 +376,10 @@ class CosyVoice2Model:
                     mel = self.flow.inference_batch(tok, rep(b["flow_prompt_speech_tokens"]), rep(b["prompt_speech_feats"]),
                                                     rep(b["flow_embeddings"])).contiguous().clone()
                 stream.synchronize()
-                with torch.cuda.stream(hift_part):
+                with torch.cuda.stream(part.hift):
                     self.hift.inference(speech_feat=mel, cache_source=zero)
-                hift_part.synchronize()
-        if est is not None:
-            est.cu_budget = 0
+                part.hift.synchronize()
+        est.cu_budget = 0
         torch.cuda.synchronize()
 
     def tts_batches(self, batches, to_host: bool = True, llm_cu_slots: Optional[int] = None, llm_loops: Optional[int] = None):
@@ -410,9 +404,16 @@ class CosyVoice2Model:
         k = self.llm_cu_slots if llm_cu_slots is None else llm_cu_slots
         n = self.llm_loops if llm_loops is None else llm_loops
         if k:
-            yield from self._tts_batches_partitioned(batches, to_host, k, max(1, n))
+            yield from pipeline.PartitionedPipeline(self, to_host, k, max(1, n)).run(batches)
         else:
-            yield from self._tts_batches_shared(batches, to_host)
+            yield from pipeline.shared_pipeline(self, batches, to_host)
+
+    def tts_batches_depth(self, llm_cu_slots: Optional[int] = None, llm_loops: Optional[int] = None) -> int:
+        """The largest number of batches ``tts_batches`` keeps between taking them from ``batches`` and their ``on_done``: what a ring
+        of per-batch buffers (cosyvoice_amd.dist.ConditioningRing) has to hold."""
+        k = self.llm_cu_slots if llm_cu_slots is None else llm_cu_slots
+        n = self.llm_loops if llm_loops is None else llm_loops
+        return pipeline.depth(max(1, n) if k else 0, self.llm_merge)
 
     def _flow_hift(self, b, toks):
         """Flow + HiFT of one batch.  Equal generated lengths (teacher-forced runs, the benchmark): one batched pass ->
@@ -423,7 +424,7 @@ class CosyVoice2Model:
         take the ragged path whatever the generated lengths."""
         n = len(toks[0])
         zero = torch.zeros(1, 1, 0)
-        if all(len(t) == n for t in toks) and not _ragged_prompts(b):
+        if all(len(t) == n for t in toks) and not ragged_prompts(b):
             tok = torch.tensor(toks, dtype=torch.int32, device=self.device)
             mel = self.flow.inference_batch(tok, b["flow_prompt_speech_tokens"], b["prompt_speech_feats"], b["flow_embeddings"])
             wav, _ = self.hift.inference(speech_feat=mel.contiguous(), cache_source=zero)
@@ -448,301 +449,6 @@ class CosyVoice2Model:
         return self.flow.inference_ragged([torch.tensor(t, dtype=torch.int32) for t in toks],
                                           [b["flow_prompt_speech_tokens"][i] for i in range(B)],
                                           [b["prompt_speech_feats"][i] for i in range(B)], b["flow_embeddings"], padded=True)
-
-    def _tts_batches_partitioned(self, batches, to_host, k, n_llm):
-        import queue
-        from collections import deque
-        from concurrent.futures import ThreadPoolExecutor
-        llm_parts, flow_part, borrow_part, prefill_parts, hift_part = self.cu_partition(k, n_llm)
-        est = getattr(getattr(self.flow, "decoder", None), "estimator", None)
-        if est is not None:
-            est.cu_budget = (32 - k) * 8   # the flow's launches run on that many CUs: its row-block kernels size their tiles for it
-        flow_full = torch.cuda.Stream(self.device)   # all CUs: the last batch's flow + HiFT run after every decode loop ended
-        caller = torch.cuda.current_stream()
-        # Admission work (drawing a batch from ``batches``, its on_start, the `ready` event) runs on a private non-blocking stream, not on the
-        # caller's: when that is the legacy default stream every operation on it — a conditioning copy, an event record — is an implicit barrier
-        # against all the CU-masked streams of the pipeline (they are blocking streams), i.e. the whole pipeline drained once per admitted
-        # batch (625 -> 638 audio-s/s at 20 passes, 639 -> 664 at 32, profiles/r03_flow_merge_sweeps.log).
-        adm = torch.cuda.Stream(self.device)
-        adm.wait_stream(caller)   # whatever the caller enqueued before the call is visible to the first batch
-        ctxs = queue.Queue()
-        for c, st, pf in zip(self.llm_contexts(n_llm), llm_parts, prefill_parts):
-            ctxs.put((c, st, pf))
-
-        def llm_job(bs, ready, borrow):
-            """One decode job over the utterances of ``bs`` (``llm_merge`` consecutive batches share one token loop: the step
-            is a weight stream, 16 rows cost 1.3x the time of 8) -> the token lists of each batch."""
-            ctx, own, pf = ctxs.get()
-            try:
-                # first batch of the run: the flow CUs are idle, decode there (more CUs, nothing to disturb)
-                stream = borrow_part if borrow else own
-                cat = lambda key: [x for b in bs for x in b[key]]
-                forced = cat("forced") if all(b.get("forced") is not None for b in bs) else None
-                t_job = time.perf_counter()
-                with torch.no_grad(), torch.cuda.stream(stream):
-                    stream.wait_event(ready)   # inputs the caller produced / the conditioning broadcast
-                    # the prefill is throughput-bound GEMM work: it runs beside flow + HiFT on their (three times larger)
-                    # CU share, the decode partition only runs the token loop
-                    toks = ctx.generate_batch(cat("texts"), cat("prompt_texts"), cat("llm_prompt_speech_tokens"),
-                                              forced=forced, steps_per_poll=64,
-                                              prefill_stream=None if (borrow or not self.prefill_on_flow_cus) else pf)
-                out, o = [], 0
-                for b in bs:
-                    out.append(toks[o:o + len(b["texts"])])
-                    o += len(b["texts"])
-                if self.pipeline_stats is not None:   # generate_batch ends with a D2H of the token buffer: the loop is drained
-                    self.pipeline_stats.append(("llm", len(bs), t_job, time.perf_counter()))
-                return out
-            finally:
-                ctxs.put((ctx, own, pf))
-                with llm_state_lock:
-                    llm_state["running"] -= 1
-
-        def split_rows(wav, counts, done):
-            """result of a flow group -> one (wav, done) per batch of the group (rows in batch order)"""
-            if isinstance(wav, list):   # ragged: per-utterance waveforms
-                out, o = [], 0
-                for c in counts:
-                    out.append((wav[o:o + c], done))
-                    o += c
-                return out
-            return [(w, done) for w in torch.split(wav, counts, dim=0)] if len(counts) > 1 else [(wav, done)]
-
-        def hift_job(mel, lens, mel_ready, t_job, counts):
-            """HiFT (+ D2H) of one flow group on its own stream over the flow CUs: the vocoder of group i fills the CUs the
-            flow of group i + 1 leaves idle (the tail round of every attention launch, tile quantisation of the row-block
-            kernels) instead of extending the flow stream's critical path (17 of a 91 ms job on all CUs).  ``lens``: frame counts of a
-            ragged group (mel padded, one ragged vocoder pass) or None."""
-            with torch.no_grad(), torch.cuda.stream(hift_part):
-                hift_part.wait_event(mel_ready)
-                mel.record_stream(hift_part)
-                if lens is None:
-                    wav, _ = self.hift.inference(speech_feat=mel, cache_source=torch.zeros(1, 1, 0))
-                else:
-                    wav, _ = self.hift.inference_ragged(mel, lengths=lens)
-                if to_host:
-                    res = split_rows([w.cpu() for w in wav] if lens is not None else wav.cpu(), counts, None)
-                    if self.pipeline_stats is not None:
-                        self.pipeline_stats.append(("flow", len(counts), t_job, time.perf_counter()))
-                    return res
-                wav = [w.clone() for w in wav] if lens is not None else wav.clone()
-                done = torch.cuda.Event()
-                done.record(hift_part)
-                return split_rows(wav, counts, done)
-
-        keys = ("flow_prompt_speech_tokens", "prompt_speech_feats", "flow_embeddings")
-
-        def flow_job(grp, srcs, readies, stream):
-            """Flow + HiFT of ``grp`` = consecutive batches whose tokens are ready (``flow_merge`` of them at most, same prompt lengths) as a single
-            pass: the row-block kernels run in whole rounds of workgroups over the stream's CUs, so 16 or 24 utterances cost less per utterance
-            than 8 (tools/flow_share_probe.py: 13.9 / 12.3 / 11.5 ms per utterance at 8 / 16 / 24 on the 192-CU share).  ``srcs``: per batch its
-            decode job's future and its index in that job.  -> one (wav, done) per batch."""
-            per_b = [lf.result()[i] for lf, i in srcs]
-            counts = [len(tb) for tb in per_b]
-            toks = [t for tb in per_b for t in tb]
-            ready_evs = []
-            for r in readies:
-                if all(r is not q for q in ready_evs):
-                    ready_evs.append(r)
-            b = grp[0] if len(grp) == 1 else None   # else concatenated on the job's stream, behind `ready` (below): never on this thread's default stream
-            merged = lambda: {k_: torch.cat([bb[k_] for bb in grp], dim=0) for k_ in keys}
-            t_job = time.perf_counter()
-            with llm_state_lock:
-                # every decode job of the run has ended and none is left to submit: the decode CUs are idle for good, so the remaining
-                # flow + HiFT passes (the pipeline's drain: up to 2 x llm_merge batches) take all CUs, not only the last batch
-                if llm_state["running"] == 0 and llm_state["all_submitted"]:
-                    stream = flow_full
-            if est is not None:   # tile sizes of the row-block kernels (and the solver graph that bakes them in) follow the CUs of the stream
-                est.cu_budget = 0 if stream is flow_full else (32 - k) * 8
-            n_t = len(toks[0])
-            equal = all(len(t) == n_t for t in toks) and not _ragged_prompts(grp[0])
-            if self.overlap_hift and (equal or self.ragged_hift):
-                with torch.no_grad(), torch.cuda.stream(stream):
-                    for r in ready_evs:
-                        stream.wait_event(r)
-                    stream.wait_stream(flow_part if stream is flow_full else flow_full)  # workspaces of the previous group
-                    if b is None:
-                        b = merged()
-                    if equal:
-                        tok = torch.tensor(toks, dtype=torch.int32, device=self.device)
-                        mel = self.flow.inference_batch(tok, b["flow_prompt_speech_tokens"], b["prompt_speech_feats"], b["flow_embeddings"])
-                        mel, lens = mel.contiguous().clone(), None   # the flow's output buffer is rewritten by the next group
-                    else:
-                        mel, lens = self._flow_ragged(b, toks)       # a padded tensor of its own
-                    mel_ready = torch.cuda.Event()
-                    mel_ready.record(stream)
-                return hift_pool.submit(hift_job, mel, lens, mel_ready, t_job, counts)   # one worker: vocoder workspaces are used in group order
-            with torch.no_grad(), torch.cuda.stream(stream):
-                for r in ready_evs:
-                    stream.wait_event(r)
-                stream.wait_stream(flow_part if stream is flow_full else flow_full)  # workspaces of the previous group
-                if self.overlap_hift:
-                    hift_pool.submit(lambda: None).result()   # earlier groups' vocoder jobs are enqueued ...
-                    stream.wait_stream(hift_part)             # ... and done with the vocoder workspaces before this one uses them
-                if b is None:
-                    b = merged()
-                wav = self._flow_hift(b, toks)
-                if to_host:
-                    res = split_rows([w.cpu() for w in wav] if isinstance(wav, list) else wav.cpu(), counts, None)
-                    if self.pipeline_stats is not None:
-                        self.pipeline_stats.append(("flow", len(grp), t_job, time.perf_counter()))
-                    return res
-                # the equal-length path returns a view of HiFT's per-shape workspace, which the next flow_job overwrites on this
-                # stream as soon as its tokens arrive: hand the consumer its own copy (made here, ordered before `done`)
-                wav = [w.clone() for w in wav] if isinstance(wav, list) else wav.clone()
-                done = torch.cuda.Event()
-                done.record(stream)
-                return split_rows(wav, counts, done)
-
-        from concurrent.futures import Future
-        flow_q, flow_cv, flow_state = deque(), threading.Condition(), {"closed": False, "abort": False}
-
-        def same_layout(a, c):
-            if _ragged_prompts(a) or _ragged_prompts(c):   # per-utterance prompt lists: such a batch is a flow pass of its own
-                return False
-            return all(a[k_].shape[1:] == c[k_].shape[1:] for k_ in keys)
-
-        def flow_worker():
-            """The flow thread: takes the oldest batch whose tokens it then waits for, adds the batches right behind it whose tokens are ALREADY
-            there (up to ``flow_merge``, same prompt lengths) and runs them as one pass — groups form across decode jobs when the flow side has
-            a backlog and never wait for tokens when it has none (the pipeline's fill)."""
-            while True:
-                with flow_cv:
-                    while not flow_q and not flow_state["closed"]:
-                        flow_cv.wait()
-                    if not flow_q:
-                        return
-                    grp = [flow_q.popleft()]
-                t0 = grp[0]
-                try:
-                    if flow_state["abort"]:
-                        raise RuntimeError("tts_batches closed before this batch was vocoded")
-                    t0["lf"].result()
-                    with flow_cv:
-                        while (len(grp) < fmerge and flow_q and flow_q[0]["lf"].done() and flow_q[0]["lf"].exception() is None
-                               and same_layout(t0["b"], flow_q[0]["b"])):
-                            grp.append(flow_q.popleft())
-                    res = flow_job([t["b"] for t in grp], [(t["lf"], t["idx"]) for t in grp], [t["ready"] for t in grp], flow_part)
-                except BaseException as e:
-                    for t in grp:
-                        t["fut"].set_exception(e)
-                    continue
-
-                def deliver(r, grp=grp):
-                    try:
-                        if hasattr(r, "result"):
-                            r = r.result()
-                        for t, x in zip(grp, r):
-                            t["fut"].set_result(x)
-                    except BaseException as e:
-                        for t in grp:
-                            if not t["fut"].done():
-                                t["fut"].set_exception(e)
-                if hasattr(res, "add_done_callback"):   # the equal-length overlap path hands back its vocoder job
-                    res.add_done_callback(deliver)
-                else:
-                    deliver(res)
-
-        def collect(fut):
-            wav, done = fut.result()
-            if done is not None:
-                caller.wait_event(done)
-            return wav
-
-        it = iter(batches)
-
-        def draw():
-            with torch.cuda.stream(adm):
-                return next(it, None)
-        nxt = draw()
-        inflight = deque()
-        first = True
-        merge = max(1, int(getattr(self, "llm_merge", 1)))
-        fmerge = max(1, int(getattr(self, "flow_merge", 1)))
-        llm_state_lock = threading.Lock()
-        llm_state = {"running": 0, "all_submitted": False}
-        # pipeline fill: the first decode jobs are small so that the flow stream gets its first batches early and is then fed without a
-        # gap while the job size grows to `merge` (1, 2, 2, 3, merge, ...: with 4 batches per job from the start the flow CUs idled ~0.2 s)
-        ramp = [int(v) for v in self.llm_ramp]
-        n_jobs = 0
-        with ThreadPoolExecutor(max_workers=n_llm) as llm_pool, ThreadPoolExecutor(max_workers=1) as flow_pool, \
-                ThreadPoolExecutor(max_workers=1) as hift_pool:
-            flow_pool.submit(flow_worker)
-            try:
-                while nxt is not None or inflight:
-                    # keep n_llm decode loops busy plus one job queued behind them.  A job is admitted only when ALL its batches fit: a job cut short
-                    # by the in-flight cap (one batch in a 4-batch slot) occupies a decode loop for 70 % of a full job's time
-                    job_batches = min(merge, ramp[n_jobs]) if n_jobs < len(ramp) else merge
-                    while nxt is not None and (not inflight or len(inflight) + job_batches <= (n_llm + 2) * merge):
-                        bs, rows = [], 0
-                        while nxt is not None and len(bs) < job_batches and rows + len(nxt["texts"]) <= self.llm.max_batch:
-                            rows += len(nxt["texts"])
-                            bs.append(nxt)
-                            nxt = draw()
-                        if not bs:
-                            raise ValueError(f"a batch of {len(nxt['texts'])} utterances exceeds the LLM's max_batch {self.llm.max_batch}")
-                        ready = torch.cuda.Event()
-                        with torch.cuda.stream(adm):
-                            for b in bs:
-                                if b.get("on_start") is not None:
-                                    b["on_start"]()   # e.g. the conditioning broadcast: same order on every rank, never from worker threads
-                            ready.record(adm)
-                        n_jobs += 1
-                        with llm_state_lock:
-                            llm_state["running"] += 1
-                            llm_state["all_submitted"] = nxt is None
-                        lf = llm_pool.submit(llm_job, bs, ready, first)
-                        with flow_cv:
-                            for i, b in enumerate(bs):
-                                t = dict(b=b, lf=lf, idx=i, ready=ready, fut=Future())
-                                flow_q.append(t)
-                                inflight.append((b, t["fut"]))
-                            flow_cv.notify()
-                        first = False
-                        job_batches = min(merge, ramp[n_jobs]) if n_jobs < len(ramp) else merge
-                    b_done, fut = inflight.popleft()
-                    try:
-                        wav = collect(fut)
-                    finally:
-                        if b_done.get("on_done") is not None:
-                            b_done["on_done"]()   # every job of this batch (decode, flow, vocoder) has ended: its conditioning slot is free
-                    yield wav
-            finally:
-                with flow_cv:   # normal end: the queue is empty; a consumer that stopped early: the flow thread fails what is left instead of running it
-                    flow_state["closed"] = True
-                    flow_state["abort"] = bool(flow_q)
-                    flow_cv.notify()
-        if est is not None:
-            est.cu_budget = 0
-
-    @torch.no_grad()
-    def _tts_batches_shared(self, batches, to_host):
-        llm_stream = self.llm_context.stream if hasattr(self.llm_context, "stream") else torch.cuda.Stream()
-        pending, pending_b = None, None
-        import itertools
-        for b in itertools.chain(batches, [None]):   # lazily: a batch takes its buffers when its turn comes
-            toks = None
-            if b is not None:
-                with torch.cuda.stream(llm_stream):
-                    if b.get("on_start") is not None:
-                        b["on_start"]()
-                    ready = torch.cuda.Event()
-                    ready.record(llm_stream)
-                    toks = self.llm.generate_batch(b["texts"], b["prompt_texts"], b["llm_prompt_speech_tokens"], forced=b.get("forced"))
-            if pending is not None:
-                if isinstance(pending, list):
-                    out = [w.cpu() for w in pending] if to_host else pending
-                else:
-                    out = pending.cpu() if to_host else pending.clone()
-                if not to_host:
-                    torch.cuda.current_stream().synchronize()   # on_done promises that nothing reads the batch's inputs any more
-                if pending_b.get("on_done") is not None:
-                    pending_b["on_done"]()
-                yield out
-                pending = None
-            if toks is not None:
-                torch.cuda.current_stream().wait_event(ready)  # conditioning of this batch is in place
-                pending, pending_b = self._flow_hift(b, toks), b
 
 
 class CosyVoiceModel(CosyVoice2Model):

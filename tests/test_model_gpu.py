@@ -339,15 +339,11 @@ def test_reload_invalidates_descriptors_and_graphs():
     assert torch.equal(m_b, m_ref) and not torch.equal(m_a, m_b)
 
 
-@pytest.mark.parametrize("cu_slots", [8, 0])
-def test_tts_batches_conditioning_slots_lifecycle(cu_slots):
-    """Batches drawn lazily from a generator, each with its own conditioning slot (cosyvoice_amd.dist.ConditioningRing): on_start runs in
-    batch order when the pipeline admits the batch, on_done once its waveform has been collected, a slot is never handed out twice at once,
-    and every batch's audio is what that batch's OWN conditioning gives (distinct prompt per batch) — CU-partitioned and shared-CU paths."""
+def _slot_batches(lc, fc, n_batches, n_slots, B=2, n_p=10):
+    """``n_batches`` batches that differ only in their conditioning (distinct prompt per batch), each drawn lazily with its own
+    ConditioningRing slot: on_start copies the batch's payload into the slot (stands in for the broadcast), on_done releases it.
+    -> (ring, batches(), events, conds, texts, forced); ``events``: ("draw" | "start" | "done", batch) in the order they happened."""
     from cosyvoice_amd import dist as cd
-    m, lc, fc, hc = _model()
-    m.llm_merge = 1
-    n_batches, B, n_p = 10, 2, 10        # more batches than slots: slots are recycled
     g = torch.Generator().manual_seed(21)
     texts = [torch.randint(0, lc.vocab_size, (1, 6), generator=g, dtype=torch.int32).cuda() for _ in range(B)]
     forced = [torch.randint(0, lc.speech_token_size, (12,), generator=g).tolist() for _ in range(B)]
@@ -360,7 +356,7 @@ def test_tts_batches_conditioning_slots_lifecycle(cu_slots):
         conds.append((pf, em, ps, pt))
     payloads = [cd.pack_conditioning(*c)[0].cuda() for c in conds]
     _, layout = cd.pack_conditioning(*conds[0])
-    ring = cd.ConditioningRing(7, layout, torch.device("cuda"))   # (llm_loops + 2) * llm_merge + llm_merge + 2: the pipeline's depth
+    ring = cd.ConditioningRing(n_slots, layout, torch.device("cuda"))
     events, live = [], set()
 
     def batches():
@@ -368,6 +364,7 @@ def test_tts_batches_conditioning_slots_lifecycle(cu_slots):
             slot = ring.acquire()
             assert slot not in live
             live.add(slot)
+            events.append(("draw", i))
 
             def start(i=i, slot=slot):
                 events.append(("start", i))
@@ -381,14 +378,50 @@ def test_tts_batches_conditioning_slots_lifecycle(cu_slots):
             pf, em, ps, pt = ring.tensors(slot)
             yield dict(texts=texts, prompt_texts=[pt] * B, llm_prompt_speech_tokens=[ps] * B, flow_prompt_speech_tokens=ps.expand(B, -1),
                        prompt_speech_feats=pf.expand(B, -1, -1), flow_embeddings=em.expand(B, -1), forced=forced, on_start=start, on_done=done)
+    return ring, batches(), events, conds, texts, forced
+
+
+@pytest.mark.parametrize("to_host", [True, False])
+@pytest.mark.parametrize("cu_slots", [8, 0])
+def test_tts_batches_conditioning_slots_lifecycle(cu_slots, to_host):
+    """Batches drawn lazily from a generator, each with its own conditioning slot (cosyvoice_amd.dist.ConditioningRing): on_start runs in
+    batch order when the pipeline admits the batch, on_done once its waveform has been collected, a slot is never handed out twice at once,
+    and every batch's audio is what that batch's OWN conditioning gives (distinct prompt per batch) — CU-partitioned and shared-CU paths,
+    waveforms copied to the host or left on the device (then on_done must also wait for the flow work that reads the slot: a slot
+    rewritten under a running flow job gives the mel of another batch's prompt)."""
+    m, lc, fc, hc = _model()
+    m.llm_merge = 1
+    n_batches, B = 10, 2        # more batches than slots: slots are recycled
+    ring, batches, events, conds, texts, forced = _slot_batches(lc, fc, n_batches, 7)   # 7 slots: more than tts_batches_depth() asks for
+    mels, orig = [], m.flow.inference_batch
+
+    def rec(tok, *a, **k):      # flow_merge = 1: one call per batch, in batch order (one flow thread / the calling thread)
+        mel = orig(tok, *a, **k)
+        mels.append((tok.clone(), mel.clone()))
+        return mel
+    m.flow.inference_batch = rec
     torch.manual_seed(0)
-    wavs = [w.clone() for w in m.tts_batches(batches(), to_host=True, llm_cu_slots=cu_slots, llm_loops=2)]
+    try:
+        wavs = [w.cpu().clone() for w in m.tts_batches(batches, to_host=to_host, llm_cu_slots=cu_slots, llm_loops=2)]
+    finally:
+        m.flow.inference_batch = orig
+    torch.cuda.synchronize()
     assert len(wavs) == n_batches and ring.in_use() == 0 and ring.high_water <= 7
+    assert ring.high_water <= m.tts_batches_depth(llm_cu_slots=cu_slots, llm_loops=2)
     starts = [i for k, i in events if k == "start"]
     dones = [i for k, i in events if k == "done"]
     assert starts == list(range(n_batches)) and dones == list(range(n_batches))
     for i in range(n_batches):
         assert events.index(("start", i)) < events.index(("done", i))
+    # the mel (deterministic) of every batch is what ITS conditioning gives: the same flow call alone, after the run
+    assert len(mels) == n_batches
+    for i, (tok, mel) in enumerate(mels):
+        pf, em, ps, pt = (t.cuda() for t in conds[i])
+        assert tok.tolist() == forced
+        solo_mel = m.flow.inference_batch(tok, ps.expand(B, -1), pf.expand(B, -1, -1), em.expand(B, -1))
+        err = (solo_mel - mel).abs().max().item()
+        print(f"batch {i}: mel vs solo {err:.3e}")
+        assert err < 1e-4
     # a batch's waveform length / content follows ITS prompt: the mel (deterministic) differs between batches with different prompts;
     # compare each batch against a solo run of the same conditioning through tts_batch (vocoder noise differs: compare lengths + energy)
     for i in (0, 4, 9):
@@ -397,6 +430,43 @@ def test_tts_batches_conditioning_slots_lifecycle(cu_slots):
         assert solo.shape == wavs[i].shape
         assert (solo.abs().mean() - wavs[i].abs().mean()).abs().item() < 0.02 * max(1e-3, solo.abs().mean().item()) + 5e-3
     m.close()
+
+
+@pytest.mark.parametrize("cu_slots", [8, 0])
+def test_tts_batches_early_close_releases_every_batch(cu_slots):
+    """A consumer that stops after two waveforms: every batch the pipeline had drawn (in flight, or looked ahead and never started) gets
+    exactly one on_done, never before its on_start, no conditioning slot leaks, the estimator's CU budget is back at 0, and a complete
+    run on the same model afterwards equals a fresh model's bit for bit."""
+    m, lc, fc, hc = _model()
+    m.llm_merge = 1
+    n_slots = m.tts_batches_depth(llm_cu_slots=cu_slots, llm_loops=2)
+    ring, batches, events, _, _, _ = _slot_batches(lc, fc, 6, n_slots)
+    gen = m.tts_batches(batches, to_host=True, llm_cu_slots=cu_slots, llm_loops=2)
+    assert len([next(gen), next(gen)]) == 2
+    gen.close()
+    drawn = [i for k, i in events if k == "draw"]
+    assert ring.in_use() == 0 and 2 <= len(drawn) <= 6
+    assert sorted(i for k, i in events if k == "done") == drawn
+    for i in drawn:
+        if ("start", i) in events:
+            assert events.index(("start", i)) < events.index(("done", i))
+    assert m.flow.decoder.estimator.cu_budget == 0
+
+    def full_run(model):
+        ring, batches, _, _, _, _ = _slot_batches(lc, fc, 6, n_slots)
+        torch.manual_seed(0)
+        wavs = [w.clone() for w in model.tts_batches(batches, to_host=True, llm_cu_slots=cu_slots, llm_loops=2)]
+        assert ring.in_use() == 0
+        return wavs
+    again = full_run(m)
+    fresh_model = _model()[0]
+    fresh_model.llm_merge = 1
+    fresh = full_run(fresh_model)
+    assert len(again) == len(fresh) == 6
+    for a, b in zip(again, fresh):
+        assert a.shape == b.shape and torch.isfinite(a).all() and torch.equal(a, b)
+    m.close()
+    fresh_model.close()
 
 
 @pytest.mark.parametrize("fm", [2, 3])

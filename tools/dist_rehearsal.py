@@ -81,7 +81,7 @@ def main():
         ps = torch.randint(0, lc.speech_token_size, pspeech.shape, generator=g, dtype=torch.int32)
         return cd.pack_conditioning(pf, em, ps, ptext)[0]
     payloads = [payload_of(i).to(dev) for i in range(args.steps)] if rank == 0 else None
-    ring = cd.ConditioningRing(12, layout, dev)
+    ring = cd.ConditioningRing(model.tts_batches_depth(), layout, dev)
     digests, samples, order = {}, {}, []
     orig = flow.inference_batch
 
