@@ -89,6 +89,10 @@ __global__ __launch_bounds__(256) void norm_kernel(const cv_norm_params p) {
 // (mean, M2) pair per (batch, group, chunk) — two-pass inside the chunk, the second read hits L2 — and pass 2 merges the pairs
 // in fixed order (Chan's parallel-variance formula: deterministic, no atomics, no E[x^2]-mean^2 cancellation) before
 // normalising its own chunk with the fused affine / Mish / time-embedding add.
+// Every value is first centred on a pilot, the (batch, group)'s own first element x[b][0][g * cpg]: one fp32 cannot hold the mean of data
+// with a large common offset (x = 1000 + N(0, 1): half an ulp of 1000 is 3e-5 of the spread), while x - pilot is exact there (Sterbenz) and
+// elsewhere rounds relative to the spread.  The chunk means, their merge and the final subtraction are all of x - pilot.  Pass 1 stores the
+// pilot next to its pair (3 floats per chunk): in place (out_f32 == x) pass 2 overwrites the pilot's cell while other chunks still need it.
 constexpr int GN_ROWS = 32;
 
 __device__ __forceinline__ float block_sum(float v, float* red) {
@@ -106,19 +110,21 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const cv_groupnorm_params
   const int t0 = chunk * GN_ROWS, nr = min(GN_ROWS, p.T - t0);
   const int n = nr * cpg;
   const float* x = p.x + (int64_t)b * p.x_bs + (int64_t)t0 * p.ldx + g * cpg;
+  const float pilot = p.x[(int64_t)b * p.x_bs + g * cpg];
   float s = 0.f;
-  for (int i = threadIdx.x; i < n; i += 256) s += x[(int64_t)(i / cpg) * p.ldx + (i % cpg)];
+  for (int i = threadIdx.x; i < n; i += 256) s += x[(int64_t)(i / cpg) * p.ldx + (i % cpg)] - pilot;
   const float mean = block_sum(s, red) / (float)n;
   float q = 0.f;
   for (int i = threadIdx.x; i < n; i += 256) {
-    const float d = x[(int64_t)(i / cpg) * p.ldx + (i % cpg)] - mean;
+    const float d = (x[(int64_t)(i / cpg) * p.ldx + (i % cpg)] - pilot) - mean;
     q += d * d;
   }
   const float m2 = block_sum(q, red);
   if (threadIdx.x == 0) {
-    float* o = p.partial + (((int64_t)b * p.groups + g) * gridDim.x + chunk) * 2;
+    float* o = p.partial + (((int64_t)b * p.groups + g) * gridDim.x + chunk) * 3;
     o[0] = mean;
     o[1] = m2;
+    o[2] = pilot;
   }
 }
 
@@ -128,11 +134,11 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const cv_groupnorm_params
   const int cpg = p.C / p.groups;
   const int nch = gridDim.x;
   // merge the chunk statistics (every thread redundantly: <= T/32 broadcast loads)
-  const float* part = p.partial + ((int64_t)b * p.groups + g) * nch * 2;
+  const float* part = p.partial + ((int64_t)b * p.groups + g) * nch * 3;
   float mean = 0.f, m2 = 0.f, cnt = 0.f;
   for (int c = 0; c < nch; ++c) {
     const float nb = (float)(min(GN_ROWS, p.T - c * GN_ROWS) * cpg);
-    const float mb = part[2 * c], qb = part[2 * c + 1];
+    const float mb = part[3 * c], qb = part[3 * c + 1];
     const float tot = cnt + nb, d = mb - mean;
     mean += d * (nb / tot);
     m2 += qb + d * d * (cnt * nb / tot);
@@ -142,9 +148,10 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const cv_groupnorm_params
   const int t0 = chunk * GN_ROWS, nr = min(GN_ROWS, p.T - t0);
   const int n = nr * cpg;
   const float* add = p.add ? p.add + (int64_t)b * p.add_ld : nullptr;
+  const float pilot = part[2];
   for (int i = threadIdx.x; i < n; i += 256) {
     const int t = t0 + i / cpg, c = g * cpg + (i % cpg);
-    float y = (p.x[(int64_t)b * p.x_bs + (int64_t)t * p.ldx + c] - mean) * rstd;
+    float y = ((p.x[(int64_t)b * p.x_bs + (int64_t)t * p.ldx + c] - pilot) - mean) * rstd;
     if (p.gamma) y *= p.gamma[c];
     if (p.beta) y += p.beta[c];
     if (p.act == CV_ACT_MISH) y = act_mish(y);
@@ -164,7 +171,7 @@ extern "C" int cv_sizeof_groupnorm_params(void) { return (int)sizeof(cv_groupnor
 
 extern "C" int64_t cv_groupnorm_workspace_floats(int32_t B, int32_t T, int32_t groups) {
   if (B <= 0 || T <= 0 || groups <= 0) return 0;
-  return (int64_t)B * groups * ((T + GN_ROWS - 1) / GN_ROWS) * 2;
+  return (int64_t)B * groups * ((T + GN_ROWS - 1) / GN_ROWS) * 3;
 }
 
 extern "C" int cv_groupnorm_cl(const cv_groupnorm_params* pp, void* stream) {

@@ -233,16 +233,21 @@ __global__ __launch_bounds__(256) void spk_stats_kernel(const float* x, int64_t 
   const int b = blockIdx.y, cl = threadIdx.x & 63, ph = threadIdx.x >> 6, c = blockIdx.x * 64 + cl;
   const int n = min(max(len[b], 0), T);
   const float* xb = x + (int64_t)b * x_bs + c;
-  const float s_ = sc ? sc[c] : 1.f, h_ = sc ? sh[c] : 0.f;
+  const bool pre = sc != nullptr;   // without the prologue the rows are pooled as they are: no ReLU either
+  const float s_ = pre ? sc[c] : 1.f, h_ = pre ? sh[c] : 0.f;
   float s = 0.f;
-  for (int t = ph; t < n; t += 4) s += fmaxf(fmaf(xb[(int64_t)t * ldx], s_, h_), 0.f);
+  for (int t = ph; t < n; t += 4) {
+    const float v = xb[(int64_t)t * ldx];
+    s += pre ? fmaxf(fmaf(v, s_, h_), 0.f) : v;
+  }
   part[ph][cl] = s;
   __syncthreads();
   const float mean = (part[0][cl] + part[1][cl] + part[2][cl] + part[3][cl]) / (float)n;
   __syncthreads();
   float q = 0.f;
   for (int t = ph; t < n; t += 4) {
-    const float d = fmaxf(fmaf(xb[(int64_t)t * ldx], s_, h_), 0.f) - mean;
+    const float v = xb[(int64_t)t * ldx];
+    const float d = (pre ? fmaxf(fmaf(v, s_, h_), 0.f) : v) - mean;
     q = fmaf(d, d, q);
   }
   part[ph][cl] = q;

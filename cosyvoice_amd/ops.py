@@ -316,7 +316,7 @@ def groupnorm_cl(x, groups, gamma, beta, eps, partial, *, act=ACT_NONE, add=None
     """x (B, T, C) fp32 channels-last (any row / batch strides); add (C,) or (B, C) fp32 added after the activation."""
     _req_cuda(x, gamma, beta, partial, add, out_f32, out_act)
     B, T, Cc = x.shape
-    assert x.stride(2) == 1 and partial.numel() >= B * groups * ((T + 31) // 32) * 2
+    assert x.stride(2) == 1 and partial.numel() >= B * groups * ((T + 31) // 32) * 3
     p = L.GroupNormParams()
     p.B, p.T, p.C, p.groups, p.eps = B, T, Cc, groups, eps
     p.x, p.x_bs, p.ldx = x.data_ptr(), x.stride(0), x.stride(1)

@@ -112,7 +112,9 @@ int cv_layernorm(const cv_norm_params* p, void* stream);
  * fused affine, optional Mish, optional per-batch-row vector added after the activation (time embedding).
  * Replaces Block1D's GroupNorm+Mish of the non-causal CFM estimator (matcha decoder Block1D via flow/decoder.py:129-130,
  * CosyVoice-v1) and InterpolateRegulator's GroupNorm (flow/length_regulator.py:36-38).  Two launches (chunk statistics,
- * merge + apply); `partial` is caller-owned scratch of cv_groupnorm_workspace_floats(B, T, groups) floats.
+ * merge + apply); `partial` is caller-owned scratch of cv_groupnorm_workspace_floats(B, T, groups) floats: per (batch, group,
+ * 32-row chunk) the chunk's mean and M2 of x - pilot and the pilot itself, pilot = x[b][0][group * C / groups], so that data with
+ * a large common offset keep the accuracy of centred data.  Sums run in a fixed order (no atomics).
  * x may alias out_f32.
  * ------------------------------------------------------------------------------------------ */
 typedef struct cv_groupnorm_params {
@@ -328,7 +330,8 @@ int cv_spk_conv(const cv_spk_conv_params* p, void* stream);
 int cv_spk_cam_gate(const float* psum, int64_t psum_bs, const int32_t* len, int32_t B, int32_t T, int32_t seg_len, const float* w1,
                     const float* b1, const float* w2, const float* b2, float* gate, int64_t gate_bs, void* stream);
 /* out[b] = [mean | unbiased std] over t < len[b] of relu(x * pre_scale + pre_shift) (BN -> ReLU, or x itself when pre_scale is
- * NULL), C channels (C % 64 == 0), len[b] >= 2 (CAMPPlus.py:35-46) */
+ * NULL), C channels (C % 64 == 0) (CAMPPlus.py:35-46).  Precondition: len[b] >= 2 for every b — the unbiased std of fewer than two frames
+ * is 0 / 0 (the reference's torch.std gives NaN there as well); the entry point does not check it, the lengths live on the device. */
 int cv_spk_stats_pool(const float* x, int64_t x_bs, int32_t ldx, const int32_t* len, int32_t B, int32_t T, int32_t C,
                       const float* pre_scale, const float* pre_shift, float* out, int64_t out_bs, void* stream);
 

@@ -413,3 +413,434 @@ def worst_ratio(got, ref, bound):
     if not bool(torch.isfinite(got).all()):
         return float("inf")
     return ((got - ref).abs() / bound.clamp_min(1e-300)).max().item()
+
+
+# ----------------------------------------------------------------------------- GroupNorm over channels-last (csrc/norm.hip: cv_groupnorm_cl)
+GN_ROWS = 32            # rows per chunk of gn_stats_kernel / gn_apply_kernel
+GN_KINDS = ("ordinary", "x30", "offset100", "offset1000", "const", "zero")
+
+
+def gn_units(B, T, C, G, g, start=0, order=GN_KINDS):
+    """(B, T, C) fp32 with one kind per (batch, group) unit — the statistics span the unit, so the kinds of flow_rows are given to whole units:
+    order[(start + b G + g) % len(order)] (order: GN_KINDS unless given): ordinary 2 N(0, 1) + 0.3, that x 30, + 100, + 1000, near-constant c + 1e-3 N(0, 1) (variance 1e-6 against
+    eps 1e-5) and zero.  Returns x and the kind of every unit."""
+    cpg = C // G
+    x = (torch.randn(B, T, G, cpg, generator=g) * 2 + 0.3)
+    kinds = []
+    for b in range(B):
+        for gi in range(G):
+            kind = order[(start + b * G + gi) % len(order)]
+            kinds.append(kind)
+            if kind == "x30":
+                x[b, :, gi] *= 30.0
+            elif kind == "offset100":
+                x[b, :, gi] += 100.0
+            elif kind == "offset1000":
+                x[b, :, gi] += 1000.0
+            elif kind == "const":
+                x[b, :, gi] = (0.5 + 0.25 * gi) + 1e-3 * torch.randn(T, cpg, generator=g)
+            elif kind == "zero":
+                x[b, :, gi] = 0.0
+    return x.reshape(B, T, C).contiguous(), kinds
+
+
+def gn_chain(T, cpg):
+    """The longest chain of fp32 additions an element's contribution passes through in the fixed summation order of cv_groupnorm_cl: the strided
+    adds of one of 256 threads over a 32-row chunk, the 6-step butterfly, the 3 adds of the wave sums, and 4 operations per merged chunk (the
+    difference, the weight, the product and the sum of Chan's update).  The n of rule 2: a sum evaluated as a tree errs by its depth, not by its
+    number of leaves."""
+    return -(-min(GN_ROWS, T) * cpg // 256) + 6 + 3 + 4 * (-(-T // GN_ROWS))
+
+
+def gn_ref64(x, G, gamma, beta, eps):
+    """GroupNorm of channels-last x (B, T, C) in float64 and a SHIFT-INVARIANT fp32 bound built from the centred values only (derivation: module
+    docstring of tests/test_norm_act_ops_gpu.py).  Returns y = (x - mu) r gamma + beta (unrounded) and its bound (before Mish / add / the rounding
+    to the output type)."""
+    B, T, C = x.shape
+    cpg = C // G
+    n = T * cpg
+    nc = gn_chain(T, cpg)
+    xg = x.double().reshape(B, T, G, cpg)
+    g = (torch.ones(C, dtype=torch.float64) if gamma is None else gamma.double()).reshape(1, 1, G, cpg)
+    b = (torch.zeros(C, dtype=torch.float64) if beta is None else beta.double()).reshape(1, 1, G, cpg)
+    eps64 = torch.tensor(eps, dtype=torch.float32).double()
+    red = lambda t: t.sum((1, 3), keepdim=True)
+    d = xg - red(xg) / n
+    q = red(d * d)
+    v = q / n + eps64
+    r = torch.rsqrt(v)
+    y = d * r * g + b
+    dmax = d.abs().amax((1, 3), keepdim=True)
+    dmu = (nc + 2) * EPS32 * red(d.abs()) / n                                  # rule 2 on the centred sum (chain of nc additions), / n
+    dd = dmu + 0.5 * EPS32 * (d.abs() + dmax) + 0.5 * ulp(d, torch.float32)    # + the rounding of x - pilot (|x - p| <= |d| + max|d|) and of - mean
+    dq = (nc + 2) * EPS32 * q + 2.0 * red(d.abs() * dd)                        # rule 2 on the squares + d(d^2) = 2 |d| dd
+    rel = 0.5 * (dq / n + 0.5 * EPS32 * v) / v + 2.0 * EPS32                   # through v^-1/2; + eps rounds once; rsqrtf <= 2 ulp
+    first = g.abs() * r * (dd + d.abs() * rel) + 1.5 * EPS32 * ((d * r * g).abs() + b.abs())
+    return y.reshape(B, T, C), (2.0 * first).reshape(B, T, C)
+
+
+def _gn_block_sum(v, n):
+    """block_sum of norm.hip over the first n entries of v (.., n) fp32: thread i adds entries i, i + 256, .. in order, each wave reduces by the
+    xor butterfly (offsets 32 .. 1), the four wave sums are added left to right."""
+    k = (n + 255) // 256
+    pad = torch.zeros(*v.shape[:-1], k * 256, dtype=torch.float32)
+    pad[..., :n] = v
+    pad = pad.reshape(*v.shape[:-1], k, 256)
+    s = pad[..., 0, :].clone()
+    for j in range(1, k):
+        s = s + pad[..., j, :]
+    s = s.reshape(*v.shape[:-1], 4, 64)
+    lane = torch.arange(64)
+    o = 32
+    while o:
+        s = s + s[..., lane ^ o]
+        o >>= 1
+    w = s[..., 0]
+    return ((w[..., 0] + w[..., 1]) + w[..., 2]) + w[..., 3]
+
+
+def gn_emulate(x, G, eps, pilot, fault=None):
+    """fp32 torch emulation of gn_stats_kernel / gn_apply_kernel in their own summation order (32-row chunks, _gn_block_sum, two-pass inside the
+    chunk, Chan's merge over the chunks in order).  pilot False: the arithmetic before the fix (chunk means of x itself, one fp32 each); True: every
+    value is first centred on the unit's own first element, x[b, 0, g cpg].  fault "full_count": the last, partial chunk is merged with the count
+    of a full one.  Returns (x - mean) rstd (B, T, C) fp32."""
+    B, T, C = x.shape
+    cpg = C // G
+    xg = x.float().reshape(B, T, G, cpg).permute(0, 2, 1, 3).contiguous()       # (B, G, T, cpg)
+    if pilot:
+        xg = xg - xg[:, :, :1, :1]
+    mean = torch.zeros(B, G)
+    m2 = torch.zeros(B, G)
+    cnt = 0.0
+    f32 = lambda a: torch.tensor(a, dtype=torch.float32)
+    for t0 in range(0, T, GN_ROWS):
+        nr = min(GN_ROWS, T - t0)
+        n = nr * cpg
+        c = xg[:, :, t0:t0 + nr].reshape(B, G, n)
+        mb = _gn_block_sum(c, n) / f32(float(n))
+        dc = c - mb[..., None]
+        qb = _gn_block_sum(dc * dc, n)
+        nb = float(GN_ROWS * cpg if fault == "full_count" else n)
+        tot = cnt + nb
+        dlt = mb - mean
+        mean = mean + dlt * (f32(nb) / f32(tot))
+        m2 = m2 + (qb + dlt * dlt * (f32(cnt) * f32(nb) / f32(tot)))
+        cnt = tot
+    rstd = torch.rsqrt(m2 / f32(cnt) + f32(eps))
+    y = (xg - mean[..., None, None]) * rstd[..., None, None]
+    return y.permute(0, 2, 1, 3).reshape(B, T, C)
+
+
+# ----------------------------------------------------------------------------- speaker encoder kernels (csrc/speaker.hip)
+FLT_EPSILON = 2.0 ** -23
+
+
+def _spk_gather(A, ti, fi, in_len, fill=None):
+    """A (B, T_in, F_in, cin) -> (B, T_out, F_out, cin): the rows (ti[t], fi[f]); positions outside [0, in_len[b]) x [0, F_in) give 0 (or
+    ``fill`` (cin,)), whatever A holds there or at the clamped index (NaN included)."""
+    B, T_in, F_in, _ = A.shape
+    okt = (ti >= 0)[None] & (ti[None] < in_len[:, None])
+    okf = (fi >= 0) & (fi < F_in)
+    g = A[:, ti.clamp(0, T_in - 1)][:, :, fi.clamp(0, F_in - 1)]
+    ok = okt[:, :, None, None] & okf[None, None, :, None]
+    other = torch.zeros((), dtype=A.dtype) if fill is None else fill.to(A.dtype)
+    return torch.where(ok, g, other)
+
+
+def _spk_taps(c):
+    tt, ff = torch.arange(c["T_out"]), torch.arange(c["F_out"])
+    kf, kt = c["k"]
+    for i_f in range(kf):
+        for i_t in range(kt):
+            yield i_f, i_t, tt * c["s"][1] + i_t * c["dt"] - c["pad"][1], ff * c["s"][0] + i_f - c["pad"][0]
+
+
+def spk_conv_ref64(c, x, w, in_len, out_len, pre=None, bias=None, res=None, gate=None):
+    """cv_spk_conv as include/cosyvoice_amd.h states it, float64, from the fp32 operands.  c: dict(T_out, F_out, k (kf, kt), s (sf, st), pad (pf,
+    pt), dt, relu, gate_seg); x (B, T_in, F_in, cin) (rows at and past in_len may hold anything), w (N, kf, kt, cin), in_len / out_len (B,) long,
+    pre (scale, shift), bias (N,), res (B, T_out, F_out, N) (rows past out_len may hold anything), gate (B, segments, N).  Returns ref (B, T_out,
+    F_out, N), rows >= out_len zero, and its bound: rule 2 with n = kf kt cin, plus one term each for the prologue fma, the bias, the residual
+    and the gate product."""
+    f64 = torch.float64
+    B = x.shape[0]
+    kf, kt = c["k"]
+    cin, N = x.shape[-1], w.shape[0]
+    A = x.double()
+    extras = 0
+    if pre is not None:
+        A = torch.clamp(A * pre[0].double() + pre[1].double(), min=0)
+        extras += 1
+    acc = torch.zeros(B, c["T_out"], c["F_out"], N, dtype=f64)
+    sabs = torch.zeros_like(acc)
+    for i_f, i_t, ti, fi in _spk_taps(c):
+        g = _spk_gather(A, ti, fi, in_len)
+        wt = w[:, i_f, i_t].double()
+        acc += g @ wt.t()
+        sabs += g.abs() @ wt.abs().t()
+    live = (torch.arange(c["T_out"])[None] < out_len[:, None])[:, :, None, None]
+    if bias is not None:
+        acc, sabs, extras = acc + bias.double(), sabs + bias.double().abs(), extras + 1
+    if res is not None:
+        r = torch.where(live, res.double(), torch.zeros((), dtype=f64))
+        acc, sabs, extras = acc + r, sabs + r.abs(), extras + 1
+    if c.get("relu"):
+        acc = torch.clamp(acc, min=0)
+    if gate is not None:
+        seg = torch.arange(c["T_out"]) // c["gate_seg"]
+        gg = torch.where(live, gate.double()[:, seg][:, :, None, :], torch.zeros((), dtype=f64))
+        acc, sabs, extras = acc * gg, sabs * gg.abs(), extras + 1
+    ref = torch.where(live, acc, torch.zeros((), dtype=f64))
+    assert bool(torch.isfinite(ref).all())
+    bound = torch.where(live, sum_bound(kf * kt * cin + extras, sabs, ref, torch.float32), torch.zeros((), dtype=f64))
+    return ref, bound
+
+
+def spk_conv_emulate(c, x, w, in_len, out_len, pre=None, bias=None, res=None, gate=None, fault=None):
+    """fp32 torch emulation of spk_conv_kernel: the prologue as one fma, K in the kernel's order (taps outer, 16 channels per step; cin = 1: all
+    taps in one step), then bias, residual, ReLU, gate, rows >= out_len zero; psum = ((v0 + v1) + v2) + v3 of the stored rows.  Returns y, psum
+    (B, ceil(T_out / 4), N) (F_out == 1) or None.  Faults: "pre_on_pad" (padded taps contribute relu(shift)), "past_len" (rows >= in_len read),
+    "no_dilation", "sf_on_time" (the frequency stride applied to time and the time stride to frequency), "gate_shift" (segment index of frame
+    t + 1), "psum_all_rows" (psum counts rows >= out_len)."""
+    f32 = torch.float32
+    B, T_in = x.shape[0], x.shape[1]
+    kf, kt = c["k"]
+    cin, N = x.shape[-1], w.shape[0]
+    c = dict(c)
+    if fault == "no_dilation":
+        c["dt"] = 1
+    if fault == "sf_on_time":
+        c["s"] = (c["s"][1], c["s"][0])
+    if fault == "past_len":
+        in_len = torch.full_like(in_len, T_in)
+    A, fill = x.float(), None
+    if pre is not None:
+        A = torch.clamp((A.double() * pre[0].double() + pre[1].double()).float(), min=0)
+        if fault == "pre_on_pad":
+            fill = torch.clamp(pre[1].float(), min=0)
+    acc = torch.zeros(B, c["T_out"], c["F_out"], N, dtype=f32)
+    if cin == 1:
+        G = torch.cat([_spk_gather(A, ti, fi, in_len, fill) for _, _, ti, fi in _spk_taps(c)], -1)
+        acc = acc + G @ w.reshape(N, kf * kt).t()
+    else:
+        for i_f, i_t, ti, fi in _spk_taps(c):
+            g = _spk_gather(A, ti, fi, in_len, fill)
+            for c0 in range(0, cin, 16):
+                acc = acc + g[..., c0:c0 + 16] @ w[:, i_f, i_t, c0:c0 + 16].t()
+    tt = torch.arange(c["T_out"])
+    live = (tt[None] < out_len[:, None])[:, :, None, None]
+    v = acc
+    if bias is not None:
+        v = v + bias
+    if res is not None:
+        v = v + torch.where(live, res.float(), torch.zeros(()))
+    if c.get("relu"):
+        v = torch.clamp(v, min=0)
+    if gate is not None:
+        seg = ((tt + 1 if fault == "gate_shift" else tt) // c["gate_seg"]).clamp(max=gate.shape[1] - 1)
+        v = v * torch.where(live, gate.float()[:, seg][:, :, None, :], torch.zeros(()))
+    y = torch.where(live, v, torch.zeros(()))
+    psum = None
+    if c["F_out"] == 1:
+        src = v if fault == "psum_all_rows" else y
+        G4 = (c["T_out"] + 3) // 4
+        p = torch.zeros(B, 4 * G4, N)
+        p[:, :c["T_out"]] = src[:, :, 0]
+        p = p.reshape(B, G4, 4, N)
+        psum = ((p[:, :, 0] + p[:, :, 1]) + p[:, :, 2]) + p[:, :, 3]
+    return y, psum
+
+
+def spk_psum_ref64(y):
+    """The 4-row group sums of the rows a launch stored (y (B, T_out, N)), float64, and rule 2 with n = 4 on them."""
+    B, T, N = y.shape
+    G4 = (T + 3) // 4
+    p = torch.zeros(B, 4 * G4, N, dtype=torch.float64)
+    p[:, :T] = y.double()
+    p = p.reshape(B, G4, 4, N)
+    ref = p.sum(2)
+    return ref, sum_bound(4, p.abs().sum(2), ref, torch.float32)
+
+
+def spk_gate_ref64(ps, lens, T, seg_len, w1, b1, w2, b2):
+    """cv_spk_cam_gate in float64 from the group sums ps (B, groups, 128) (groups at and past ceil(len / 4) may hold anything).  Returns gate
+    (B, ceil(T / seg_len), 32) — segments at and past a length zero — its bound, and e32 of the sigmoid.  Bound: rule 2 on the two group sums
+    (n = the groups each spans) and the two divisions, pushed through |w1|, rule 2 with n = 128 + 1, through |w2|, rule 2 with n = 64 + 1, then
+    the sigmoid: Lipschitz 1 / 4 and rule 3 (expf and the reciprocal)."""
+    f64 = torch.float64
+    B = ps.shape[0]
+    nseg = (T + seg_len - 1) // seg_len
+    ref, bound = torch.zeros(B, nseg, 32, dtype=f64), torch.zeros(B, nseg, 32, dtype=f64)
+    W1, W2 = w1.double(), w2.double()
+    vs, live = [], []
+    for b in range(B):
+        n = min(max(int(lens[b]), 0), T)
+        groups = (n + 3) // 4
+        p = ps[b, :groups].double()
+        for s in range(nseg):
+            if s * seg_len >= n:
+                continue
+            g0, g1 = s * (seg_len // 4), min(groups, (s + 1) * (seg_len // 4))
+            cnt = min(seg_len, n - s * seg_len)
+            tot, seg = p.sum(0), p[g0:g1].sum(0)
+            ctx = tot / n + seg / cnt
+            bctx = ((groups + 2) * EPS32 * p.abs().sum(0) / n + (g1 - g0 + 2) * EPS32 * p[g0:g1].abs().sum(0) / cnt
+                    + EPS32 * ((tot / n).abs() + (seg / cnt).abs()) + 0.5 * EPS32 * ctx.abs())
+            pre = W1 @ ctx + b1.double()
+            bh = W1.abs() @ bctx + sum_bound(129, W1.abs() @ (ctx.abs() + bctx) + b1.double().abs(), pre, torch.float32)
+            hid = torch.clamp(pre, min=0)
+            v = W2 @ hid + b2.double()
+            bv = W2.abs() @ bh + sum_bound(65, W2.abs() @ (hid + bh) + b2.double().abs(), v, torch.float32)
+            ref[b, s], bound[b, s] = torch.sigmoid(v), 0.25 * bv
+            vs.append(v)
+            live.append((b, s))
+    e32 = torch.zeros((), dtype=f64)
+    if vs:
+        v = torch.stack(vs)
+        e32 = (torch.sigmoid(v.float()).double() - torch.sigmoid(v.float().double())).abs().max()
+        for (b, s) in live:
+            bound[b, s] += act_bound(e32, ref[b, s])
+    return ref, bound, e32.item()
+
+
+def spk_gate_emulate(ps, lens, T, seg_len, w1, b1, w2, b2, fault=None):
+    """fp32 torch emulation of spk_cam_gate_kernel: group sums in 4 slices (groups i = slice mod 4, in order) added in slice order, the hidden
+    layer in 8 slices of 16 channels, the output in 8 slices of 8, partials added to the bias in slice order, 1 / (1 + exp(-v)).  fault "seg_len":
+    the last segment is divided by seg_len instead of its valid frames."""
+    B = ps.shape[0]
+    nseg = (T + seg_len - 1) // seg_len
+    out = torch.zeros(B, nseg, 32)
+
+    def sliced(p):
+        parts = []
+        for ph in range(4):
+            a = torch.zeros(128)
+            for i in range(ph, p.shape[0], 4):
+                a = a + p[i]
+            parts.append(a)
+        return ((parts[0] + parts[1]) + parts[2]) + parts[3]
+    for b in range(B):
+        n = min(max(int(lens[b]), 0), T)
+        groups = (n + 3) // 4
+        p = ps[b, :groups].float()
+        for s in range(nseg):
+            if s * seg_len >= n:
+                continue
+            g0, g1 = s * (seg_len // 4), min(groups, (s + 1) * (seg_len // 4))
+            cnt = seg_len if fault == "seg_len" else min(seg_len, n - s * seg_len)
+            ctx = sliced(p) / float(n) + sliced(p[g0:g1]) / float(cnt)
+            h = b1.float().clone()
+            for sl in range(8):
+                h = h + w1[:, sl * 16:(sl + 1) * 16].float() @ ctx[sl * 16:(sl + 1) * 16]
+            hid = torch.clamp(h, min=0)
+            v = b2.float().clone()
+            for sl in range(8):
+                v = v + w2[:, sl * 8:(sl + 1) * 8].float() @ hid[sl * 8:(sl + 1) * 8]
+            out[b, s] = 1.0 / (1.0 + torch.exp(-v))
+    return out
+
+
+def spk_pool_ref64(x, lens, pre=None):
+    """cv_spk_stats_pool in float64: [mean | unbiased std] over t < len of a = relu(x scale + shift) (x itself without pre); x (B, T, C), every
+    len >= 2.  Returns ref (B, 2 C), its first-order bound (derivation: module docstring of tests/test_speaker_ops_gpu.py) and e32 of sqrt."""
+    f64 = torch.float64
+    B, T, Cc = x.shape
+    ref, bound = torch.zeros(B, 2 * Cc, dtype=f64), torch.zeros(B, 2 * Cc, dtype=f64)
+    stds = []
+    for b in range(B):
+        n = int(lens[b])
+        a = x[b, :n].double()
+        da = torch.zeros_like(a)
+        if pre is not None:
+            a = torch.clamp(a * pre[0].double() + pre[1].double(), min=0)
+            da = 0.5 * EPS32 * a
+        mu = a.sum(0) / n
+        d = a - mu
+        q = (d * d).sum(0)
+        var = q / (n - 1)
+        std = torch.sqrt(var)
+        dmu = ((n + 2) * EPS32 * a.abs().sum(0) + da.sum(0)) / n + 0.5 * EPS32 * mu.abs()
+        dd = dmu + da + 0.5 * ulp(d, torch.float32)
+        dq = (n + 2) * EPS32 * q + 2.0 * (d.abs() * dd).sum(0)
+        dvar = 2.0 * (dq / (n - 1) + 0.5 * EPS32 * var)
+        dstd = torch.minimum(dvar / (2.0 * std).clamp_min(1e-300), torch.sqrt(dvar))
+        ref[b] = torch.cat([mu, std])
+        bound[b] = torch.cat([2.0 * dmu, dstd])
+        stds.append(var)
+    v32 = torch.stack(stds).float()
+    e32 = (torch.sqrt(v32).double() - torch.sqrt(v32.double())).abs().max()
+    bound[:, Cc:] += act_bound(e32, ref[:, Cc:])
+    return ref, bound, e32.item()
+
+
+def spk_pool_emulate(x, lens, pre=None, fault=None):
+    """fp32 torch emulation of spk_stats_kernel: 4 row phases (t = phase mod 4, in order) added in phase order, two passes, sqrt(q / (n - 1)).
+    fault "biased": q / n."""
+    B, T, Cc = x.shape
+    out = torch.zeros(B, 2 * Cc)
+
+    def phased(a):
+        parts = []
+        for ph in range(4):
+            s = torch.zeros(Cc)
+            for t in range(ph, a.shape[0], 4):
+                s = s + a[t]
+            parts.append(s)
+        return ((parts[0] + parts[1]) + parts[2]) + parts[3]
+    for b in range(B):
+        n = int(lens[b])
+        a = x[b, :n].float()
+        if pre is not None:
+            a = torch.clamp((a.double() * pre[0].double() + pre[1].double()).float(), min=0)
+        mean = phased(a) / float(n)
+        d = a - mean
+        out[b] = torch.cat([mean, torch.sqrt(phased(d * d) / float(n if fault == "biased" else n - 1))])
+    return out
+
+
+def spk_log_cmn_ref64(mel, lens, cmn):
+    """cv_spk_log_cmn in float64: log(max(mel, FLT_EPSILON)) (- its mean over t < len when cmn), rows >= len zero; mel (B, T, n_mels) (rows at and
+    past a length may hold anything).  Bound: rule 3 for logf, rule 2 (n = len terms) + the division for the mean, one rounding for the
+    difference.  Returns ref, bound, e32."""
+    f64 = torch.float64
+    B, T, nm = mel.shape
+    ref, bound = torch.zeros(B, T, nm, dtype=f64), torch.zeros(B, T, nm, dtype=f64)
+    m32 = torch.clamp(torch.nan_to_num(mel.float(), nan=1.0), min=FLT_EPSILON)
+    e32 = (torch.log(m32).double() - torch.log(m32.double())).abs().max()
+    for b in range(B):
+        n = min(max(int(lens[b]), 0), T)
+        if n == 0:
+            continue
+        l = torch.log(torch.clamp(mel[b, :n].double(), min=FLT_EPSILON))
+        bl = 4.0 * torch.maximum(e32, EPS32 * l.abs())
+        if cmn:
+            mean = l.sum(0) / n
+            bmean = ((n + 2) * EPS32 * l.abs().sum(0) + bl.sum(0)) / n + 0.5 * EPS32 * mean.abs()
+            ref[b, :n] = l - mean
+            bound[b, :n] = bl + bmean + 0.5 * ulp(ref[b, :n], torch.float32)
+        else:
+            ref[b, :n], bound[b, :n] = l, bl
+    return ref, bound, e32.item()
+
+
+def spk_log_cmn_emulate(mel, lens, cmn, fault=None):
+    """fp32 torch emulation of spk_log_cmn_kernel: P = 1024 / n_mels row phases summed in order, partials added in phase order.  fault "mean_T":
+    the mean runs over all T rows."""
+    B, T, nm = mel.shape
+    P = 1024 // nm
+    out = torch.zeros(B, T, nm)
+    for b in range(B):
+        n = min(max(int(lens[b]), 0), T)
+        if n == 0:
+            continue
+        l = torch.log(torch.fmax(mel[b].float(), torch.tensor(FLT_EPSILON)))            # fmaxf: a NaN operand gives the other one
+        if cmn:
+            rows = T if fault == "mean_T" else n
+            a = torch.zeros(nm)
+            for ph in range(min(P, rows)):
+                s = torch.zeros(nm)
+                for t in range(ph, rows, P):
+                    s = s + l[t]
+                a = a + s
+            l = l - a / float(max(rows, 1))
+        out[b, :n] = l[:n]
+    return out

@@ -71,6 +71,15 @@ def test_argument_validation_returns_status_codes_without_a_gpu():
     assert lib.cv_hift_decode_enqueue(None, null) < 0
 
 
+def test_groupnorm_workspace_size_without_a_gpu():
+    """cv_groupnorm_workspace_floats: 3 floats (mean and M2 of x - pilot, and the pilot) per (batch, group, 32-row chunk); 0 for empty shapes."""
+    from cosyvoice_amd import _lib as L
+    f = L.lib().cv_groupnorm_workspace_floats
+    f.restype = ctypes.c_int64
+    assert f(1, 1, 1) == 3 and f(2, 32, 8) == 2 * 8 * 3 and f(2, 33, 8) == 2 * 8 * 2 * 3 and f(1, 500, 8) == 8 * 16 * 3
+    assert f(0, 5, 8) == 0 and f(1, 0, 8) == 0 and f(1, 5, 0) == 0
+
+
 def _variant_blocks():
     """Parameter blocks that pass every check of their entry point (dummy aligned pointers, never dereferenced: nothing may be launched
     with them), paired with the entry point and the (variant field, out-of-range value) to set."""
@@ -196,6 +205,7 @@ def test_version_and_unbound_entry_points_reject_null_arguments():
 _HELPERS, _GRAPH = "test_helper_kernels_gpu", ("test_flow_gpu", "use_graph = True")
 _LLM_OPS = "test_llm_ops_gpu"
 _FLOWBLOCK = "test_flowblock_ops_gpu"
+_SPK_OPS, _NORM_ACT = "test_speaker_ops_gpu", "test_norm_act_ops_gpu"
 COVERAGE = {
     "cv_version": "test_abi_cpu", "cv_arch": "test_abi_cpu",
     "cv_gemm": "test_gemm_modes_gpu", "cv_layernorm": "test_gemm_gpu", "cv_attention": "test_attention_ops_gpu",
@@ -208,9 +218,9 @@ COVERAGE = {
     "cv_skinny_gemm": _LLM_OPS, "cv_pack_skinny": _LLM_OPS, "cv_rmsnorm_reduce": _LLM_OPS, "cv_rope_append": _LLM_OPS,
     "cv_decode_attention": _LLM_OPS, "cv_kv_retile": _LLM_OPS, "cv_sample_ras": "test_llm_gpu",
     "cv_sizeof_skinny_params": "lifecycle", "cv_sizeof_sample_params": "lifecycle",
-    "cv_anti_alias_act": "test_bigvgan_gpu", "cv_anti_alias_act_cl": "test_bigvgan_gpu",
+    "cv_anti_alias_act": _NORM_ACT, "cv_anti_alias_act_cl": _NORM_ACT,
     "cv_stft_magnitude": _HELPERS, "cv_log_clamp_channels_first": _HELPERS,
-    "cv_groupnorm_cl": "test_flow_v1_gpu", "cv_groupnorm_workspace_floats": ("test_flow_v1_gpu", "ops.groupnorm_workspace"),
+    "cv_groupnorm_cl": _NORM_ACT, "cv_groupnorm_workspace_floats": (_NORM_ACT, "ops.groupnorm_workspace"),
     "cv_interp_linear_cl": _HELPERS, "cv_sizeof_groupnorm_params": "lifecycle", "cv_relpos_append": _HELPERS,
     "cv_sizeof_tblock_params": "lifecycle", "cv_tblock_head": _FLOWBLOCK, "cv_tblock_tail": _FLOWBLOCK,
     "cv_tblock_tail_head": _FLOWBLOCK,
@@ -222,9 +232,8 @@ COVERAGE = {
     "cv_flow_euler_graph_destroy": "lifecycle",
     "cv_sizeof_hift_decode_desc": "lifecycle", "cv_sizeof_hift_stage": "lifecycle", "cv_sizeof_hift_resunit": "lifecycle",
     "cv_hift_decode_enqueue": "test_hift_gpu", "cv_hift_decode": "test_abi_cpu", "cv_hift_decode_graph_create": "lifecycle",
-    "cv_spk_power": ("test_speaker_gpu", "test_fbank_matches_restatement"), "cv_spk_log_cmn": ("test_speaker_gpu", "test_fbank_matches_restatement"),
-    "cv_sizeof_spk_conv_params": "lifecycle",
-    "cv_spk_conv": "test_speaker_gpu", "cv_spk_cam_gate": "test_speaker_gpu", "cv_spk_stats_pool": "test_speaker_gpu",
+    "cv_spk_power": _SPK_OPS, "cv_spk_log_cmn": _SPK_OPS, "cv_sizeof_spk_conv_params": "lifecycle",
+    "cv_spk_conv": _SPK_OPS, "cv_spk_cam_gate": _SPK_OPS, "cv_spk_stats_pool": _SPK_OPS,
 }
 
 

@@ -138,6 +138,45 @@ def test_layernorm_modes(dim, rpg, act, odt):
     assert rel < {torch.float32: 1e-6, torch.bfloat16: 5e-3, torch.float16: 6e-4}[odt], f"relative L2 {rel:.3e}"
 
 
+@pytest.mark.parametrize("odt", DTS)
+@pytest.mark.parametrize("mode", ["ln", "leaky", "rms", "plain"])
+@pytest.mark.parametrize("dim", [1028, 2048])
+def test_layernorm_wide_leaky_rms_and_null_affine(dim, mode, odt):
+    """dim above 1024 (norm_kernel<., 8>: 1028 = 257 float4, one past four per lane, and the limit 2048); CV_ACT_LEAKY, which is ReLU in this
+    kernel; RMSNorm with a null beta; LayerNorm with null gamma and beta.  Rows x = 1000 + N(0, 1) for the LayerNorm modes, 3 N(0, 1) + 1 for
+    RMS; float64 reference; test_layernorm_modes' bounds, buffers and add (after the activation, one vector per row group)."""
+    from cosyvoice_amd import ops
+    g_ = torch.Generator().manual_seed(dim + len(mode))
+    rows, rpg, scale = 37, 5, 0.5
+    rms = mode == "rms"
+    x = torch.randn(rows, dim, generator=g_) * 3 + 1 if rms else 1000.0 + torch.randn(rows, dim, generator=g_)
+    g = None if mode == "plain" else torch.randn(dim, generator=g_)
+    b = None if mode in ("plain", "rms") else torch.randn(dim, generator=g_)
+    add = torch.randn((rows + rpg - 1) // rpg, dim, generator=g_)
+    xd = x.double()
+    if rms:
+        y = xd * torch.rsqrt(xd.pow(2).mean(-1, keepdim=True) + torch.tensor(1e-6, dtype=torch.float32).double()) * g.double()
+    else:
+        y = F.layer_norm(xd, (dim,), None if g is None else g.double(), None if b is None else b.double(), 1e-5)
+    if mode == "leaky":
+        y = F.relu(y)
+    ref = (y + add.double().repeat_interleave(rpg, 0)[:rows]) * scale
+    xin, addin = H.nan_like((rows + 2, dim + 8), torch.float32), H.nan_like((add.shape[0], dim + 12), torch.float32)
+    xin[:rows, :dim], addin[:, :dim] = x.cuda(), add.cuda()
+    o32, oa = H.nan_like((rows + 2, dim + 4), torch.float32), H.nan_like((rows + 2, dim + 8), odt)
+    ops.layernorm(xin[:rows, :dim], None if g is None else g.cuda(), None if b is None else b.cuda(), 1e-6 if rms else 1e-5, rms=rms,
+                  add=addin[:, :dim], rows_per_group=rpg, act=ops.ACT_LEAKY if mode == "leaky" else ops.ACT_NONE, out_scale=scale,
+                  out_f32=o32[:rows, :dim], out_act=oa[:rows, :dim])
+    torch.cuda.synchronize()
+    o32, oa = o32.cpu(), oa.cpu()
+    for o in (o32, oa):
+        assert bool(torch.isnan(o[rows:].float()).all()) and bool(torch.isnan(o[:, dim:].float()).all()), "layernorm wrote outside (rows, dim)"
+    err = (o32[:rows, :dim].double() - ref).abs().max().item()
+    assert err < 2e-5 * ref.abs().max().item() + 1e-5, f"max|err| {err:.3e}, max|ref| {ref.abs().max().item():.3e}"
+    rel = ((oa[:rows, :dim].double() - ref).norm() / ref.norm()).item()
+    assert rel < {torch.float32: 1e-6, torch.bfloat16: 5e-3, torch.float16: 6e-4}[odt], f"relative L2 {rel:.3e}"
+
+
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
 def test_tall_gemm_tile_plain_and_swiglu(dt):
     """>= 8192 rows with N, K >= 512 take the 8-wave 128 x 128 tile (the LLM prefill of a 4-batch decode job): plain epilogue with a
