@@ -335,6 +335,56 @@ def style_lib():
     return _style_lib
 
 
+# ---- per-sequence LoRA (include/cosyvoice_amd_lora.h, csrc/lora.hip): its own header, export list and size handshake
+LORA_ADD, LORA_STORE, LORA_SWIGLU = 0, 1, 2
+
+
+class LoraSegment(C.Structure):
+    _fields_ = [("n_begin", _i32), ("n_end", _i32), ("u_off", _i32)]
+
+
+class LoraShrinkParams(C.Structure):
+    _fields_ = [
+        ("dtype", _i32), ("rows", _i32), ("rows_per_seq", _i32), ("K", _i32), ("R_tot", _i32), ("n_slots", _i32),
+        ("x", _vp), ("ldx", _i32),
+        ("A", _vp), ("row_adapter", _vp),
+        ("u", _vp), ("ldu", _i32),
+    ]
+
+
+class LoraExpandParams(C.Structure):
+    _fields_ = [
+        ("dtype", _i32), ("rows", _i32), ("rows_per_seq", _i32), ("N", _i32), ("r", _i32), ("n_slots", _i32), ("mode", _i32), ("n_seg", _i32),
+        ("seg", LoraSegment * 3),
+        ("u", _vp), ("ldu", _i32),
+        ("B", _vp), ("s", _vp), ("row_adapter", _vp),
+        ("y", _vp), ("ldy", _i32),
+        ("h", _vp), ("ldh", _i32),
+    ]
+
+
+LORA_EXPORTS = ["cv_sizeof_lora_shrink_params", "cv_lora_shrink", "cv_sizeof_lora_expand_params", "cv_lora_expand"]
+
+_lora_lib = None
+
+
+def lora_lib():
+    """The library with the LoRA entry points bound: checks that it exports every LORA_EXPORTS name and that the two parameter blocks
+    have the size the C side compiled (first use only)."""
+    global _lora_lib
+    if _lora_lib is None:
+        so = lib()
+        for name in LORA_EXPORTS:
+            if not hasattr(so, name):
+                raise RuntimeError(f"{LIB_PATH} does not export {name}: rebuild it with `python -m cosyvoice_amd.build`")
+        for name, st in (("lora_shrink", LoraShrinkParams), ("lora_expand", LoraExpandParams)):
+            fn = getattr(so, f"cv_sizeof_{name}_params")
+            if fn() != C.sizeof(st):
+                raise RuntimeError(f"ABI mismatch for cv_{name}_params: C {fn()} vs ctypes {C.sizeof(st)}")
+        _lora_lib = so
+    return _lora_lib
+
+
 TORCH_DT = {torch.float32: CV_F32, torch.bfloat16: CV_BF16, torch.float16: CV_F16}
 DT_TORCH = {v: k for k, v in TORCH_DT.items()}
 

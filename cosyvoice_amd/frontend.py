@@ -351,12 +351,15 @@ def assemble_vc(source_speech_token, prompt_speech_feat, prompt_speech_token, em
             "flow_embedding": embedding}
 
 
-def assemble_batch(texts, prompt_texts, speech_feats, speech_tokens, embeddings, resample_rate=24000):
+def assemble_batch(texts, prompt_texts, speech_feats, speech_tokens, embeddings, resample_rate=24000, adapters=None):
     """B prompts -> the arguments of ``CosyVoice2Model.tts_batch`` by name (also one ``tts_batches`` batch).  ``speech_feats``: per
     utterance (1, T_b, 80); ``speech_tokens``: per utterance (N_b,) / (1, N_b); ``embeddings`` (B, 192).  Each prompt is trimmed as
     ``assemble_zero_shot`` trims it.  Prompts that end up with the same lengths are stacked — (B, Np) tokens, (B, Tp, 80) feats, the
-    equal-shape flow pass; otherwise the entries are lists of (Np_b,) / (Tp_b, 80) and the flow runs its ragged pass."""
+    equal-shape flow pass; otherwise the entries are lists of (Np_b,) / (Tp_b, 80) and the flow runs its ragged pass.  ``adapters``: per
+    utterance the LoRA adapter of the LLM's attached bank (``tts_batch``'s ``adapters``; None = the base path)."""
     B = len(texts)
+    if adapters is not None and len(adapters) != B:
+        raise ValueError("one adapter per utterance")
     if not (len(prompt_texts) == len(speech_feats) == len(speech_tokens) == embeddings.shape[0] == B) or B == 0:
         raise ValueError("one text, prompt text, prompt mel, token row and embedding row per utterance")
     feats, toks = [], []
@@ -371,7 +374,7 @@ def assemble_batch(texts, prompt_texts, speech_feats, speech_tokens, embeddings,
             "llm_prompt_speech_tokens": [t.unsqueeze(0) for t in toks],
             "flow_prompt_speech_tokens": torch.stack(toks) if same else toks,
             "prompt_speech_feats": torch.stack(feats) if same else feats,
-            "flow_embeddings": embeddings}
+            "flow_embeddings": embeddings, "adapters": None if adapters is None else list(adapters)}
 
 
 class PromptFrontEnd:
@@ -428,6 +431,6 @@ class PromptFrontEnd:
         feats, emb = self.prompt_features([prompt_speech_16k], resample_rate)
         return assemble_vc(source_speech_token, feats[0], prompt_speech_token, emb)
 
-    def batch(self, texts, prompt_texts, prompt_speech_16k, speech_tokens, resample_rate=24000):
+    def batch(self, texts, prompt_texts, prompt_speech_16k, speech_tokens, resample_rate=24000, adapters=None):
         feats, emb = self.prompt_features(prompt_speech_16k, resample_rate)
-        return assemble_batch(texts, prompt_texts, feats, speech_tokens, emb, resample_rate)
+        return assemble_batch(texts, prompt_texts, feats, speech_tokens, emb, resample_rate, adapters)

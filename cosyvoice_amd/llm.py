@@ -15,7 +15,7 @@ Batching: B <= 16 sequences per step share every weight read (the reference is b
 """
 import copy
 import math
-from typing import Dict, Generator, List, Optional
+from typing import Dict, Generator, List, Optional, Union
 
 import torch
 
@@ -60,6 +60,7 @@ class Qwen2LM:
         self._loaded = False
         self._graphs: Dict[int, ops.Graph] = {}
         self._prefill_ws: Dict[tuple, dict] = {}
+        self._lora = None            # attach_lora: the bank + this context's LoRA step buffers
 
     def to(self, *a, **k):
         return self
@@ -120,6 +121,9 @@ class Qwen2LM:
         ctx = copy.copy(self)          # shares every weight tensor (they are never written after load_state_dict)
         ctx._graphs, ctx._prefill_ws = {}, {}
         ctx._alloc_state()
+        if self._lora is not None:
+            ctx._lora = None
+            ctx.attach_lora(self._lora["bank"])   # the bank is shared, the step buffers are per context
         return ctx
 
     def _alloc_state(self):
@@ -273,6 +277,178 @@ class Qwen2LM:
         ops.rmsnorm_reduce(cur, self.g_final, cfg.rms_eps, st["xn"], B, slabs=st["slabs"], nslab=KS, slab_stride=self._rp(B) * H, ld_slab=H)
         self._head_and_sample(B, use_forced, use_uniforms)
 
+    # ------------------------------------------------------------------ per-sequence LoRA (cosyvoice_amd/lora.py)
+    def attach_lora(self, bank):
+        """Make ``adapters=`` available: allocates this context's LoRA step buffers (the bank itself is shared between contexts).
+        Calls without ``adapters`` are unaffected: same launches, same graph keys, same buffers."""
+        assert self._loaded
+        if bank.cfg is not self.cfg and bank.cfg != self.cfg:
+            raise ValueError("the LoraBank was built for another LM configuration")
+        if bank.dtype != self.dtype or bank.device != self.device:
+            raise ValueError("the LoraBank's dtype / device differ from the LM's")
+        self.detach_lora()
+        cfg, dev, R = self.cfg, self.device, self.R
+        z = lambda *s, dtype=torch.float32: torch.zeros(*s, device=dev, dtype=dtype)
+        self._lora = dict(bank=bank, u=z(R, 3 * bank.r), gu=z(R, 2 * cfg.intermediate_size),
+                          slabs=z(self.DOWN_KSPLIT + 1, 32, cfg.hidden_size),
+                          row_adapter=torch.full((R,), -1, device=dev, dtype=torch.int32), ws={})
+        return self
+
+    def detach_lora(self):
+        if self._lora is None:
+            return
+        bank_id = id(self._lora["bank"])
+        keys = [k for k in self._graphs if len(k) >= 2 and k[-2:] == ("lora", bank_id)]
+        if keys:
+            torch.cuda.synchronize()
+            for k in keys:
+                self._graphs.pop(k).destroy()
+        self._lora = None
+
+    def _set_adapters(self, adapters, B):
+        """``adapters`` (one entry per row: a name, a slot, -1) -> the device row_adapter array of this context; None = base path."""
+        if adapters is None:
+            return False
+        if self._lora is None:
+            raise RuntimeError("adapters= needs attach_lora(bank) first")
+        if len(adapters) != B:
+            raise ValueError(f"adapters has {len(adapters)} entries for {B} rows")
+        bank = self._lora["bank"]
+        ra = torch.full((self.R,), -1, dtype=torch.int32)
+        ra[:B] = torch.tensor([bank.resolve(a) for a in adapters], dtype=torch.int32)
+        self._lora["row_adapter"].copy_(ra)
+        return True
+
+    def _lora_delta(self, x, A, B_, y, rows, rps=1, mode=L.LORA_ADD, segments=None, h=None, u=None, ldy=None):
+        lo = self._lora
+        u = lo["u"] if u is None else u
+        ops.lora_shrink(x, A, lo["row_adapter"], u, rows, rps)
+        ops.lora_expand(u, B_, lo["bank"].s, lo["row_adapter"], y, rows, rps, mode=mode, segments=segments, h=h, ldy=ldy)
+
+    def _head_and_sample_lora(self, B, use_forced, use_uniforms):
+        cfg, st, bank = self.cfg, self.st, self._lora["bank"]
+        ops.skinny_gemm(st["xn"], self.p_dec, B, cfg.out_vocab, cfg.hidden_size, bias=self.dec_b, out_f32=st["logits"], ldo=self.Vpad,
+                        max_wgs=2 * self.cu_budget)
+        self._lora_delta(st["xn"], bank.A_dec, bank.B_dec, st["logits"], B)
+        ops.sample_ras(self._sample_params(B, use_forced, use_uniforms))   # writes the BASE speech_embedding row (llm.py:874)
+
+    def _decode_step_lora(self, B, use_forced=False, use_uniforms=False):
+        """The decode step with the low-rank terms spliced in between the base kernels, each row with row_adapter[row].  Always the
+        split form (the normalised rows must exist in memory for the shrink): per layer rmsnorm_reduce -> QKV -> +LoRA -> attention ->
+        o_proj (in-place residual) -> +LoRA -> rmsnorm -> gate/up pre-activations (fp32) -> +LoRA, SwiGLU -> down split-K slabs ->
+        LoRA as one more slab."""
+        cfg, st, lo = self.cfg, self.st, self._lora
+        bank = lo["bank"]
+        H, I = cfg.hidden_size, cfg.intermediate_size
+        qkv_dim = cfg.q_dim + 2 * cfg.kv_dim
+        KS = self.DOWN_KSPLIT
+        scale = 1.0 / math.sqrt(cfg.head_dim)
+        ss = self._rp(B) * H
+        slabs = lo["slabs"]
+        plane = slabs.view(-1)[KS * ss:KS * ss + B * H].view(B, H)      # the LoRA slab of down_proj
+        x = st["x"]
+        for li, (lay, lb) in enumerate(zip(self.layers, bank.layers)):
+            if li > 0:
+                ops.rmsnorm_reduce(x, lay["g_in"], cfg.rms_eps, st["xn"], B, slabs=slabs, nslab=KS + 1, slab_stride=ss, ld_slab=H)
+            else:
+                ops.rmsnorm_reduce(x, lay["g_in"], cfg.rms_eps, st["xn"], B)
+            ops.skinny_gemm(st["xn"], lay["p_qkv"], B, qkv_dim, H, bias=lay["bqkv"], out_f32=st["qkv"], ldo=qkv_dim)
+            self._lora_delta(st["xn"], lb["A_qkv"], lb["B_qkv"], st["qkv"], B, segments=bank.qkv_segments)
+            ops.decode_attention(st["q"], self.kcache[li], self.vtcache[li], st["pos"], 1, st["ao"], B, cfg.num_heads,
+                                 cfg.num_kv_heads, self.ctx_max, scale, qkv=st["qkv"], inv_freq=self.rope_table)
+            ops.skinny_gemm(st["ao"], lay["p_o"], B, H, cfg.q_dim, mode=1, out_f32=x, ldo=H)
+            self._lora_delta(st["ao"], lb["A_o"], lb["B_o"], x, B)
+            ops.rmsnorm_reduce(x, lay["g_post"], cfg.rms_eps, st["xn"], B)
+            ops.skinny_gemm(st["xn"], lay["p_gu"], B, 2 * I, H, out_f32=lo["gu"], ldo=2 * I)
+            self._lora_delta(st["xn"], lb["A_gu"], lb["B_gu"], lo["gu"], B, mode=L.LORA_SWIGLU, segments=bank.gu_segments, h=st["h"])
+            ops.skinny_gemm(st["h"], lay["p_down"], B, H, I, ksplit=KS, out_f32=slabs, ldo=H, slab_stride=ss, max_wgs=self.cu_budget)
+            self._lora_delta(st["h"], lb["A_down"], lb["B_down"], plane, B, mode=L.LORA_STORE)
+        ops.rmsnorm_reduce(x, self.g_final, cfg.rms_eps, st["xn"], B, slabs=slabs, nslab=KS + 1, slab_stride=ss, ld_slab=H)
+        self._head_and_sample_lora(B, use_forced, use_uniforms)
+
+    def _step_lora(self, B, use_forced, use_uniforms):
+        if not self.use_graph:
+            self._decode_step_lora(B, use_forced, use_uniforms)
+            return
+        key = self._graph_key(B, use_forced, use_uniforms) + ("lora", id(self._lora["bank"]))
+        g = self._graphs.get(key)
+        if g is None:
+            g = ops.Graph().capture(lambda: self._decode_step_lora(B, use_forced, use_uniforms))
+            self._graphs[key] = g
+        g.launch()
+
+    def _lora_workspace(self, B, Lp):
+        lo = self._lora
+        key = (B, Lp)
+        ops.bound_cache(lo["ws"], key)
+        if key not in lo["ws"]:
+            rows = B * Lp
+            e = lambda *s: torch.empty(*s, device=self.device, dtype=torch.float32)
+            lo["ws"][key] = dict(u=e(rows, 3 * lo["bank"].r), gu=e(rows, 2 * self.cfg.intermediate_size))
+        return lo["ws"][key]
+
+    def _prefill_lora(self, B, Lp, use_forced, use_uniforms, lens=None):
+        """_prefill with the low-rank terms spliced around the same GEMMs over the B * Lp rows (row_adapter[row // Lp])."""
+        cfg, dev, st, lo = self.cfg, self.device, self.st, self._lora
+        bank = lo["bank"]
+        H = cfg.hidden_size
+        ws, lw = self._prefill_workspace(B, Lp), self._lora_workspace(B, Lp)
+        rows = B * Lp
+        x, u = ws["x"], lw["u"]
+        st["pos"].zero_()
+        scale = 1.0 / math.sqrt(cfg.head_dim)
+        klen = None
+        if lens is not None and any(l != Lp for l in lens):
+            klen = torch.tensor(list(lens), dtype=torch.int32, device=dev)
+        for li, (lay, lb) in enumerate(zip(self.layers, bank.layers)):
+            ops.layernorm(x, lay["g_in"], None, cfg.rms_eps, rms=True, out_act=ws["xn"])
+            ops.linear(ws["xn"], lay["wqkv"], bias=lay["bqkv"], out_f32=ws["qkv"])
+            self._lora_delta(ws["xn"], lb["A_qkv"], lb["B_qkv"], ws["qkv"], rows, Lp, segments=bank.qkv_segments, u=u)
+            ops.rope_append(ws["qkv"], st["pos"], rows, Lp, cfg.num_heads, cfg.num_kv_heads, self.inv_freq, ws["q"], self._k_rm,
+                            self._vt_rm, self.ctx_max)
+            ops.attention(ws["q"], self._k_rm, self._vt_rm, ws["ao"], B=B, H=cfg.num_heads, Hkv=cfg.num_kv_heads, Tq=Lp,
+                          Tk=Lp, scale=scale, q_bs=Lp * cfg.q_dim, ldq=cfg.q_dim, k_bs=cfg.num_kv_heads * self.ctx_max * 64,
+                          k_hs=self.ctx_max * 64, ldk=64, vt_ld=self.ctx_max, o_bs=Lp * cfg.q_dim, ldo=cfg.q_dim, causal=True,
+                          klen=klen)
+            ops.kv_retile(self._k_rm, self._vt_rm, self.kcache[li], self.vtcache[li], B, cfg.num_kv_heads, self.ctx_max, Lp)
+            ops.linear(ws["ao"], lay["wo"], res=x, out_f32=x)
+            self._lora_delta(ws["ao"], lb["A_o"], lb["B_o"], x, rows, Lp, u=u)
+            ops.layernorm(x, lay["g_post"], None, cfg.rms_eps, rms=True, out_act=ws["xn"])
+            ops.linear(ws["xn"], lay["wgu"], out_f32=lw["gu"])      # the [gate16 | up16] pre-activations, no epilogue
+            self._lora_delta(ws["xn"], lb["A_gu"], lb["B_gu"], lw["gu"], rows, Lp, mode=L.LORA_SWIGLU, segments=bank.gu_segments,
+                             h=ws["h"], u=u)
+            ops.linear(ws["h"], lay["wdown"], res=x, out_f32=x)
+            self._lora_delta(ws["h"], lb["A_down"], lb["B_down"], x, rows, Lp, u=u)
+        if klen is None:
+            st["x"][:B].copy_(x.view(B, Lp, H)[:, Lp - 1])
+            st["pos"][:B].fill_(Lp - 1)
+        else:
+            last = (klen - 1).long()
+            st["x"][:B].copy_(x.view(B, Lp, H)[torch.arange(B, device=dev), last])
+            st["pos"][:B].copy_(klen - 1)
+        ops.rmsnorm_reduce(st["x"], self.g_final, cfg.rms_eps, st["xn"], B)
+        self._head_and_sample_lora(B, use_forced, use_uniforms)
+
+    def _assemble_lora(self, ws, texts, prompt_texts, prompt_speech, B, Lp):
+        """The adapted rows of the prefill assembly (llm.py:840,849): embed_tokens(text) and speech_embedding(prompt speech) are module
+        calls and get e += s (A^T[idx]) B^T; the sos / task rows (llm_embedding.weight[...], :846-847) stay base rows."""
+        lo = self._lora
+        bank, ra = lo["bank"], lo["row_adapter"]
+        slots = ra[:B].tolist()
+        x = ws["x"].view(B, Lp, -1)
+        for b in range(B):
+            if slots[b] < 0:
+                continue
+            t = torch.cat([prompt_texts[b].reshape(-1), texts[b].reshape(-1)]).to(self.device).long()
+            ps = prompt_speech[b].reshape(-1).to(self.device).long()
+            lt = t.numel()
+            for idx, AT, Bk, r0 in ((t, bank.AT_embed, bank.B_embed, 1), (ps, bank.AT_speech, bank.B_speech, 2 + lt)):
+                n = idx.numel()
+                if n == 0:
+                    continue
+                u = AT[slots[b]].index_select(0, idx).to(torch.float32)       # the gather of A^T (n, r)
+                ops.lora_expand(u, Bk, bank.s, ra[b:b + 1], x[b, r0:r0 + n], n, n)
+
     def _graph_key(self, B, use_forced, use_uniforms):
         """Key of a captured step: the launch shape plus every option that changes the step's launches or their arguments."""
         return (B, use_forced, use_uniforms, self.seed, self.cu_budget, self.top_p, self.top_k, self.fallback_mode, self.top_p2, self.top_k2,
@@ -383,7 +559,8 @@ class Qwen2LM:
                        forced: Optional[List[List[int]]] = None, uniforms: Optional[torch.Tensor] = None,
                        max_token_text_ratio: float = 20, min_token_text_ratio: float = 2, steps_per_poll: int = 16,
                        max_steps: Optional[int] = None, prefill_stream=None,
-                       lm_inputs: Optional[List[torch.Tensor]] = None) -> List[List[int]]:
+                       lm_inputs: Optional[List[torch.Tensor]] = None,
+                       adapters: Optional[List[Union[int, str]]] = None) -> List[List[int]]:
         """Run B sequences (any mix of text / prompt lengths) to completion; returns the emitted token lists.
         ``lm_inputs``: per sequence a ready-made prefill embedding sequence (L_b, hidden) fp32 instead of the
         [sos, embed(prompt_text + text), task_id, speech_emb(prompt_speech)] assembly — the hook for the fork's other LM
@@ -391,11 +568,16 @@ class Qwen2LM:
         [sos, spk, fused phoneme sequence, task_id, prompt speech]); ``texts`` still gives the min/max length ratios.
         ``prefill_stream``: run the prefill (throughput-bound GEMMs / attention over B*Lp rows) on that stream instead of the
         current one — model.tts_batches hands it a stream on the flow stage's CUs, so the few-CU decode partition only ever
-        runs the latency-bound token loop."""
+        runs the latency-bound token loop.
+        ``adapters`` (after attach_lora): per sequence a LoRA adapter of the attached bank, by name or slot, -1 = base model only.
+        With ``lm_inputs`` the ready-made embeddings are taken as they are: only the stack and the head are adapted."""
         assert self._loaded
         B = len(texts)
         assert 1 <= B <= self.max_batch
         st = self.st
+        lora = self._set_adapters(adapters, B)
+        prefill = self._prefill_lora if lora else self._prefill
+        step = self._step_lora if lora else self._step
         if lm_inputs is not None:
             assert len(lm_inputs) == B and all(e.dim() == 2 and e.shape[1] == self.cfg.hidden_size for e in lm_inputs)
             lens = [int(e.shape[0]) for e in lm_inputs]
@@ -431,17 +613,21 @@ class Qwen2LM:
             prefill_stream.wait_stream(cur)            # the state resets above
             with torch.cuda.stream(prefill_stream):
                 self._assemble(ws, texts, prompt_texts, prompt_speech, B, Lp, lm_inputs)
-                self._prefill(B, Lp, use_forced, use_uniforms, lens)
+                if lora and lm_inputs is None:
+                    self._assemble_lora(ws, texts, prompt_texts, prompt_speech, B, Lp)
+                prefill(B, Lp, use_forced, use_uniforms, lens)
             cur.wait_stream(prefill_stream)            # KV caches, first token and decode state are in place
         else:
             self._assemble(ws, texts, prompt_texts, prompt_speech, B, Lp, lm_inputs)
-            self._prefill(B, Lp, use_forced, use_uniforms, lens)
+            if lora and lm_inputs is None:
+                self._assemble_lora(ws, texts, prompt_texts, prompt_speech, B, Lp)
+            prefill(B, Lp, use_forced, use_uniforms, lens)
         limit = int(mx[:B].max()) if max_steps is None else max_steps
         done_steps = 1
         while done_steps < limit:
             n = min(steps_per_poll, limit - done_steps)
             for _ in range(n):
-                self._step(B, use_forced, use_uniforms)
+                step(B, use_forced, use_uniforms)
             done_steps += n
             if bool((st["finished"][:B] != 0).all().item()):
                 break
@@ -455,10 +641,13 @@ class Qwen2LM:
     @torch.no_grad()
     def inference(self, text, text_len, prompt_text, prompt_text_len, prompt_speech_token, prompt_speech_token_len, embedding,
                   sampling: int = 25, max_token_text_ratio: float = 20, min_token_text_ratio: float = 2,
-                  lm_input: Optional[torch.Tensor] = None, nonce: Optional[int] = None) -> Generator[int, None, None]:
+                  lm_input: Optional[torch.Tensor] = None, nonce: Optional[int] = None,
+                  adapters: Optional[List[Union[int, str]]] = None) -> Generator[int, None, None]:
         """Reference signature (llm.py:823-836).  Yields python ints as they become available (polled every 8 steps).
-        ``lm_input`` (L, hidden): a ready-made prefill embedding sequence (see generate_batch)."""
+        ``lm_input`` (L, hidden): a ready-made prefill embedding sequence (see generate_batch).  ``adapters``: one entry, the LoRA
+        adapter of this request (see generate_batch)."""
         assert self._loaded
+        lora = self._set_adapters(adapters, 1)
         text_len += prompt_text_len  # the reference mutates text_len in place (llm.py:839)
         st = self.st
         B = 1
@@ -475,7 +664,9 @@ class Qwen2LM:
         st["max_len"].fill_(max_len)
         self._new_request_nonce(nonce)
         self._assemble(ws, [text], [prompt_text], [prompt_speech_token], B, Lp, None if lm_input is None else [lm_input])
-        self._prefill(B, Lp, False, False)
+        if lora and lm_input is None:
+            self._assemble_lora(ws, [text], [prompt_text], [prompt_speech_token], B, Lp)
+        (self._prefill_lora if lora else self._prefill)(B, Lp, False, False)
         sent, steps = 0, 1
         while True:
             fin = int(st["finished"][0].item())
@@ -490,19 +681,20 @@ class Qwen2LM:
                 break
             n = min(8, max_len - steps)
             for _ in range(n):
-                self._step(B, False, False)
+                (self._step_lora if lora else self._step)(B, False, False)
             steps += n
 
     # teacher-forced log-probs for parity tests (not on the product path of tts())
     @torch.no_grad()
     def forced_logits(self, text, prompt_text, prompt_speech, forced: List[int], rows: int = 1,
-                      keep: Optional[List[int]] = None) -> torch.Tensor:
+                      keep: Optional[List[int]] = None, adapters: Optional[List[Union[int, str]]] = None) -> torch.Tensor:
         """Returns (len(forced)+1, V) log-softmax rows: prefill + one row per forced token (SURVEY.md H1 parity contract).
         ``rows`` > 1: the same sequence in every one of ``rows`` batch rows (the launch shapes of a batched token loop: 8-row,
         16-row and two-row-group skinny kernels, batched decode attention), result (n, rows, V).  ``keep``: only these step
-        indices are returned (in that order)."""
+        indices are returned (in that order).  ``adapters``: one LoRA adapter per row (see generate_batch)."""
         st = self.st
         B = rows
+        lora = self._set_adapters(adapters, B)
         assert 1 <= B <= self.max_batch and len(forced) + 1 <= self.max_out
         Lp = 1 + prompt_text.numel() + text.numel() + 1 + prompt_speech.numel()
         assert Lp + len(forced) + 1 <= self.ctx_max, "ctx_max too small"
@@ -516,13 +708,15 @@ class Qwen2LM:
         f[:B, :len(forced)] = torch.tensor(forced, dtype=torch.int32)
         st["forced"].copy_(f)
         self._assemble_inputs(ws, [text] * B, [prompt_text] * B, [prompt_speech] * B, B, Lp)
+        if lora:
+            self._assemble_lora(ws, [text] * B, [prompt_text] * B, [prompt_speech] * B, B, Lp)
         want = set(range(len(forced) + 1)) if keep is None else set(keep)
         got = {}
-        self._prefill(B, Lp, True, False)
+        (self._prefill_lora if lora else self._prefill)(B, Lp, True, False)
         if 0 in want:
             got[0] = st["logits"][:B, :self.cfg.out_vocab].clone()
         for i in range(1, len(forced) + 1):
-            self._step(B, True, False)
+            (self._step_lora if lora else self._step)(B, True, False)
             if i in want:
                 got[i] = st["logits"][:B, :self.cfg.out_vocab].clone()
         order = list(range(len(forced) + 1)) if keep is None else list(keep)

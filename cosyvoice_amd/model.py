@@ -137,7 +137,14 @@ class CosyVoice2Model:
             self._req_pool.append(pair)
             self._req_pool_lock.notify()
 
-    def llm_job(self, text, prompt_text, llm_prompt_speech_token, llm_embedding, uuid_, seed=None):
+    def sync_lora(self, ctx):
+        """A decode context made before ``self.llm.attach_lora(bank)`` (or before the bank was replaced) takes the LM's current bank."""
+        mine = getattr(self.llm, "_lora", None)
+        if mine is not None and (ctx._lora is None or ctx._lora["bank"] is not mine["bank"]):
+            ctx.attach_lora(mine["bank"])
+        return ctx
+
+    def llm_job(self, text, prompt_text, llm_prompt_speech_token, llm_embedding, uuid_, seed=None, lora=None):
         # model.py:116-128.  The fork's phoneme LMs (Qwen2LM_Phoneme_Src2.inference, llm.py:1687-1699) take
         # text = (bpe ids, phoneme factors) and matching length tuples: tuples are passed through in that form.
         dev = self.device
@@ -151,11 +158,15 @@ class CosyVoice2Model:
         kw = dict(text=text_a, text_len=text_len, prompt_text=ptext_a, prompt_text_len=ptext_len,
                   prompt_speech_token=llm_prompt_speech_token.to(self.device),
                   prompt_speech_token_len=torch.tensor([llm_prompt_speech_token.shape[1]], dtype=torch.int32), embedding=llm_embedding)
+        if lora is not None:   # the request's LoRA adapter (a name or slot of the bank attached to self.llm, -1 = base model)
+            kw["adapters"] = [lora]
         try:
             if hasattr(self.llm, "new_context"):
                 pair = self._acquire_llm()
                 try:
                     ctx, stream = pair
+                    if lora is not None:
+                        self.sync_lora(ctx)
                     with self.lock:
                         self._llm_spans[uuid_] = [time.perf_counter(), None]
                         while len(self._llm_spans) > 64:
@@ -221,15 +232,16 @@ class CosyVoice2Model:
 
     def tts(self, text, flow_embedding, llm_embedding=torch.zeros(0, 192), prompt_text=torch.zeros(1, 0, dtype=torch.int32),
             llm_prompt_speech_token=torch.zeros(1, 0, dtype=torch.int32), flow_prompt_speech_token=torch.zeros(1, 0, dtype=torch.int32),
-            prompt_speech_feat=torch.zeros(1, 0, 80), stream=False, speed=1.0, **kwargs):
-        # model.py:368-424
+            prompt_speech_feat=torch.zeros(1, 0, 80), stream=False, speed=1.0, lora=None, **kwargs):
+        # model.py:368-424.  ``lora`` (extra keyword): this request's LoRA adapter of the bank attached to the LLM (name, slot, -1 = base)
         this_uuid = str(uuid.uuid1())
         with self.lock:
             self.tts_speech_token_dict[this_uuid], self.llm_end_dict[this_uuid] = [], False
             self.hift_cache_dict[this_uuid] = None
         # ``seed`` (extra keyword, absent from the reference): Philox key material of this request's sampler; None draws it from
         # torch's global generator (as the reference samples from the global RNG), an int makes the request reproducible
-        p = threading.Thread(target=self.llm_job, args=(text, prompt_text, llm_prompt_speech_token, llm_embedding, this_uuid, kwargs.get("seed")))
+        p = threading.Thread(target=self.llm_job, args=(text, prompt_text, llm_prompt_speech_token, llm_embedding, this_uuid, kwargs.get("seed")),
+                             kwargs={} if lora is None else {"lora": lora})
         p.start()
 
         def check_llm():
@@ -279,12 +291,13 @@ class CosyVoice2Model:
     @torch.no_grad()
     def tts_batch(self, texts: List[torch.Tensor], prompt_texts: List[torch.Tensor], llm_prompt_speech_tokens: List[torch.Tensor],
                   flow_prompt_speech_tokens: torch.Tensor, prompt_speech_feats: torch.Tensor, flow_embeddings: torch.Tensor,
-                  forced: Optional[List[List[int]]] = None, to_host: bool = True):
+                  forced: Optional[List[List[int]]] = None, to_host: bool = True, adapters=None):
         """B utterances (texts / prompts of any lengths) through LLM -> flow -> HiFT.  Returns wav (B,S) when all sequences
         generated the same number of tokens (teacher-forced), else a list of B waveforms.  ``flow_prompt_speech_tokens`` /
         ``prompt_speech_feats`` may be lists of per-utterance (Np_b,) / (2 * Np_b, 80) tensors (prompts of different lengths): the
-        result is then always a list."""
-        toks = self.llm.generate_batch(texts, prompt_texts, llm_prompt_speech_tokens, forced=forced)
+        result is then always a list.  ``adapters``: per utterance a LoRA adapter of the bank attached to the LLM (Qwen2LM.generate_batch)."""
+        toks = self.llm.generate_batch(texts, prompt_texts, llm_prompt_speech_tokens, forced=forced,
+                                       **({} if adapters is None else {"adapters": adapters}))
         wav = self._flow_hift(dict(flow_prompt_speech_tokens=flow_prompt_speech_tokens, prompt_speech_feats=prompt_speech_feats,
                                    flow_embeddings=flow_embeddings), toks)
         if isinstance(wav, list):   # sequences of different generated lengths

@@ -565,3 +565,41 @@ def decode_attention(q, kcache, vtcache, ctx_len, ctx_add, out, B, Hq, Hkv, ctx_
 
 def sample_ras(params):
     L.check(L.lib().cv_sample_ras(C.byref(params), L.stream_ptr()), "cv_sample_ras")
+
+
+# ----------------------------------------------------------------------------- per-sequence LoRA (include/cosyvoice_amd_lora.h)
+def lora_shrink(x, A, row_adapter, u, rows, rows_per_seq=1):
+    """u[row, :R_tot] = A[a] @ x[row] with a = row_adapter[row // rows_per_seq] (a < 0: zeros).  x (>= rows, K) 16-bit rows,
+    A (n_slots, R_tot, K) 16-bit bank, row_adapter device int32, u (>= rows, >= R_tot) fp32."""
+    _req_cuda(x, A, row_adapter, u)
+    assert A.dim() == 3 and A.is_contiguous() and A.dtype == x.dtype and row_adapter.dtype == torch.int32 and u.dtype == torch.float32
+    p = L.LoraShrinkParams()
+    p.dtype, p.rows, p.rows_per_seq = L.TORCH_DT[x.dtype], rows, rows_per_seq
+    p.n_slots, p.R_tot, p.K = A.shape
+    p.x, p.ldx, p.A, p.row_adapter = x.data_ptr(), x.stride(0), A.data_ptr(), row_adapter.data_ptr()
+    p.u, p.ldu = u.data_ptr(), u.stride(0)
+    L.check(L.lora_lib().cv_lora_shrink(C.byref(p), L.stream_ptr()), "cv_lora_shrink")
+
+
+def lora_expand(u, B, s, row_adapter, y, rows, rows_per_seq=1, *, mode=L.LORA_ADD, segments=None, h=None, ldy=None):
+    """y[row, n] (+)= s[a] * B[a][n] . u[row, u_off(n):u_off(n) + r] (cv_lora_expand).  B (n_slots, N, r) 16-bit bank, s (n_slots,) fp32,
+    ``segments``: up to three (n_begin, n_end, u_off), default one segment over [0, N) at u_off 0.  mode LORA_SWIGLU: y holds the fp32
+    [gate16 | up16] pre-activations, h (>= rows, >= N / 2) 16-bit gets silu(g) * up."""
+    _req_cuda(u, B, s, row_adapter, y, h)
+    assert B.dim() == 3 and B.is_contiguous() and row_adapter.dtype == torch.int32 and u.dtype == torch.float32
+    assert y.dtype == torch.float32 and s.dtype == torch.float32
+    p = L.LoraExpandParams()
+    p.dtype, p.rows, p.rows_per_seq, p.mode = L.TORCH_DT[B.dtype], rows, rows_per_seq, mode
+    p.n_slots, p.N, p.r = B.shape
+    segments = [(0, p.N, 0)] if segments is None else list(segments)
+    if len(segments) > 3:
+        raise ValueError("cv_lora_expand takes at most three column segments")
+    p.n_seg = len(segments)
+    for i, (b, e, o) in enumerate(segments):
+        p.seg[i].n_begin, p.seg[i].n_end, p.seg[i].u_off = b, e, o
+    p.u, p.ldu, p.B, p.s, p.row_adapter = u.data_ptr(), u.stride(0), B.data_ptr(), s.data_ptr(), row_adapter.data_ptr()
+    p.y, p.ldy = y.data_ptr(), (y.stride(-2) if ldy is None else ldy)
+    if h is not None:
+        assert h.dtype == B.dtype
+        p.h, p.ldh = h.data_ptr(), h.stride(0)
+    L.check(L.lora_lib().cv_lora_expand(C.byref(p), L.stream_ptr()), "cv_lora_expand")

@@ -109,6 +109,36 @@ def consumer_copy(wav, to_host, stream):
     return wav, done
 
 
+def merged_adapters(bs):
+    """The optional per-utterance ``"llm_adapters"`` lists of the batches one decode job merges, concatenated in row order like their
+    texts; None when no batch carries the key.  A merge in which only some batches carry it is refused: the rows of the others would
+    silently fall to the base model or to a neighbour's voice."""
+    have = [b.get("llm_adapters") is not None for b in bs]
+    if not any(have):
+        return None
+    if not all(have):
+        raise ValueError(f"llm_adapters is set on {sum(have)} of the {len(bs)} batches merged into one decode job: set it on all or none")
+    for b in bs:
+        if len(b["llm_adapters"]) != len(b["texts"]):
+            raise ValueError(f"llm_adapters has {len(b['llm_adapters'])} entries for a batch of {len(b['texts'])} utterances")
+    return [a for b in bs for a in b["llm_adapters"]]
+
+
+def decode_job(ctx, bs, **kw):
+    """One ``generate_batch`` of ``ctx`` over the utterances of the batches ``bs`` -> the token lists of each batch."""
+    cat = lambda key: [x for b in bs for x in b[key]]
+    forced = cat("forced") if all(b.get("forced") is not None for b in bs) else None
+    adapters = merged_adapters(bs)
+    if adapters is not None:
+        kw["adapters"] = adapters
+    toks = ctx.generate_batch(cat("texts"), cat("prompt_texts"), cat("llm_prompt_speech_tokens"), forced=forced, **kw)
+    out, o = [], 0
+    for b in bs:
+        out.append(toks[o:o + len(b["texts"])])
+        o += len(b["texts"])
+    return out
+
+
 def _call(b, name):
     if b.get(name) is not None:
         b[name]()
@@ -139,7 +169,7 @@ def shared_pipeline(model, batches, to_host):
                     _call(b, "on_start")
                     ready = torch.cuda.Event()
                     ready.record(llm_stream)
-                    toks = model.llm.generate_batch(b["texts"], b["prompt_texts"], b["llm_prompt_speech_tokens"], forced=b.get("forced"))
+                    toks = decode_job(model.llm, [b])[0]
             if pending is not None:
                 out, done = consumer_copy(pending, to_host, torch.cuda.current_stream())
                 if done is not None:
@@ -189,20 +219,14 @@ class PartitionedPipeline:
         try:
             # first batch of the run: the flow CUs are idle, decode there (more CUs, nothing to disturb)
             stream = self.part.borrow if borrow else own
-            cat = lambda key: [x for b in bs for x in b[key]]
-            forced = cat("forced") if all(b.get("forced") is not None for b in bs) else None
             t_job = time.perf_counter()
+            if merged_adapters(bs) is not None:
+                m.sync_lora(ctx)
             with torch.no_grad(), torch.cuda.stream(stream):
                 stream.wait_event(ready)   # inputs the caller produced / the conditioning broadcast
                 # the prefill is throughput-bound GEMM work: it runs beside flow + HiFT on their (three times larger)
                 # CU share, the decode partition only runs the token loop
-                toks = ctx.generate_batch(cat("texts"), cat("prompt_texts"), cat("llm_prompt_speech_tokens"),
-                                          forced=forced, steps_per_poll=64,
-                                          prefill_stream=None if (borrow or not m.prefill_on_flow_cus) else pf)
-            out, o = [], 0
-            for b in bs:
-                out.append(toks[o:o + len(b["texts"])])
-                o += len(b["texts"])
+                out = decode_job(ctx, bs, steps_per_poll=64, prefill_stream=None if (borrow or not m.prefill_on_flow_cus) else pf)
             if m.pipeline_stats is not None:   # generate_batch ends with a D2H of the token buffer: the loop is drained
                 m.pipeline_stats.append(("llm", len(bs), t_job, time.perf_counter()))
             return out

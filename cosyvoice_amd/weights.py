@@ -287,6 +287,43 @@ def llm_state_dict(cfg: LlmConfig, seed: int = 1986, round_to=None):
     return sd
 
 
+LLM_LORA_LINEARS = ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.o_proj", "mlp.gate_proj", "mlp.up_proj",
+                    "mlp.down_proj")
+
+
+def llm_lora_modules(cfg: LlmConfig):
+    """(module name, kind, in_features / vocab, out_features / dim) of every module of the reference Qwen2LM that
+    loralib.replace_specific_layer_4lora wraps (loralib/utils.py:102-214): the seven Linears of each decoder layer, llm_decoder, and
+    the Embeddings / Linear that Qwen2LM.inference never calls as modules (llm_embedding, lm_head) or calls in the prefill assembly only
+    (embed_tokens, speech_embedding)."""
+    H, I = cfg.hidden_size, cfg.intermediate_size
+    dims = {"self_attn.q_proj": (H, cfg.q_dim), "self_attn.k_proj": (H, cfg.kv_dim), "self_attn.v_proj": (H, cfg.kv_dim),
+            "self_attn.o_proj": (cfg.q_dim, H), "mlp.gate_proj": (H, I), "mlp.up_proj": (H, I), "mlp.down_proj": (I, H)}
+    mods = [("llm.model.model.embed_tokens", "embedding", cfg.vocab_size, H)]
+    for i in range(cfg.num_layers):
+        mods += [(f"llm.model.model.layers.{i}.{n}", "linear", *dims[n]) for n in LLM_LORA_LINEARS]
+    mods += [("llm.model.lm_head", "linear", H, cfg.vocab_size), ("llm_embedding", "embedding", 2, H),
+             ("llm_decoder", "linear", H, cfg.out_vocab), ("speech_embedding", "embedding", cfg.out_vocab, H)]
+    return mods
+
+
+def llm_lora_state_dict(cfg: LlmConfig, r: int = 16, seed: int = 1986, gain: float = 0.02, round_to=None):
+    """A synthetic LoRA-only checkpoint of the speech LM with the reference's key names (``<module>.lora_A`` (r, in) and
+    ``<module>.lora_B`` (out, r), loralib/layers.py:49-50,150-151), key-seeded like every other fixture, with NON-ZERO B (a trained
+    adapter; the reference initialises B = 0).  Linear: A ~ N(0, 1 / in), B ~ N(0, gain^2 / r), so the low-rank term of a unit-rms input
+    has standard deviation about ``gain`` per output.  Embedding: A ~ N(0, 1) (the reference's init), B ~ N(0, (0.02 gain)^2 / r)
+    against base rows of N(0, 0.02^2)."""
+    specs: List[Spec] = []
+    for name, kind, n_in, n_out in llm_lora_modules(cfg):
+        if kind == "linear":
+            specs.append((f"{name}.lora_A", (r, n_in), "normal", 1.0 / math.sqrt(n_in)))
+            specs.append((f"{name}.lora_B", (n_out, r), "normal", gain / math.sqrt(r)))
+        else:
+            specs.append((f"{name}.lora_A", (r, n_in), "normal", 1.0))
+            specs.append((f"{name}.lora_B", (n_out, r), "normal", 0.02 * gain / math.sqrt(r)))
+    return materialize(specs, seed, round_to)
+
+
 def fold_weight_norm(sd: Dict[str, torch.Tensor], name: str) -> torch.Tensor:
     """w = g * v / ||v||, norm over dims (1,2) per index of dim 0 (legacy torch weight_norm, dim=0);
     for ConvTranspose1d that is per *input* channel."""
