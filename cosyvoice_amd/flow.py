@@ -12,7 +12,9 @@ key names.  All arithmetic runs in libcosyvoice_amd.so: channels-last activation
 Beyond the reference (which is batch-1 only, flow.py:277): ``inference_batch`` runs B equal-shape utterances in
 one pass (the CFG pair of every utterance is batched: 2B sequences per estimator call).
 """
+import collections
 import math
+import threading
 from typing import Dict, List, Optional
 
 import torch
@@ -781,7 +783,11 @@ class CausalMaskedDiffWithXvec:
         self.decoder = CausalConditionalCFM(self.cfg, ConditionalDecoder(self.cfg, dtype, self.device), self.device)
         self._loaded = False
         self._bufs: Dict[tuple, dict] = {}
-        self._stream_caches: Dict[object, "EncoderStreamCache"] = {}   # cache_key of a streaming request -> its encoder cache
+        # cache_key of a streaming request -> its encoder cache, least recently used first; every access under _stream_lock
+        # (chunk calls come from the request threads under the model's flow_lock, drop_stream_cache from their clean-up without it)
+        self._stream_caches = collections.OrderedDict()
+        self._stream_lock = threading.Lock()
+        self.stream_cache_cap = 8      # caches kept at most (about 60 MB each); the model raises it to its max_llm_requests
         self.stream_enc_cache = True   # keep a streaming request's encoder state between its chunk calls (see ``inference``)
 
     def to(self, *a, **k):
@@ -833,7 +839,7 @@ class CausalMaskedDiffWithXvec:
         ``stream_cache`` (EncoderStreamCache, B = 1): a streaming request's chunk call — the encoder only runs on the rows behind
         the cached chunk-causal prefix (UpsampleConformerEncoder.forward_tokens_cached)."""
         assert self._loaded
-        cfg, dev = self.cfg, self.device
+        dev = self.device
         B, Ng = tokens.shape
         Np = prompt_tokens.shape[1]
         Nv = Np + Ng                       # real tokens
@@ -844,15 +850,7 @@ class CausalMaskedDiffWithXvec:
         lb = int(getattr(self, "length_bucket", 0) or 0)
         N = -(-Nv // lb) * lb if lb > 0 else Nv
         padded = lb > 0                    # with bucketing on, an exact fit also takes the masked path: one graph per bucket
-        T = 2 * N
-        D = embeddings.shape[1]
-        bf = self._buffers(B, N, D)
-        # speaker: F.normalize -> Linear (flow.py:286-287); RMSNorm kernel with scale 1/sqrt(D) == x / ||x||
-        bf["emb_in"].copy_(embeddings.to(dev, torch.float32))
-        ops.layernorm(bf["emb_in"], None, None, 1e-24 / D, rms=True, out_scale=1.0 / math.sqrt(D), out_act=bf["emb_n"][:, :D])
-        ops.gemm(bf["emb_n"], self.spk_w, B, cfg.output_size, D, lda=bf["emb_n"].stride(0), bias=self.spk_b, out_f32=bf["spks"],
-                 ldo32=cfg.output_size)
-        # tokens -> embedding -> encoder -> encoder_proj = mu (flow.py:290-302)
+        bf = self._buffers(B, N, embeddings.shape[1])
         bf["idx"][:, :Np].copy_(prompt_tokens.to(dev, torch.int32))
         bf["idx"][:, Np:Nv].copy_(tokens.to(dev, torch.int32))
         klen_enc = klen_est = None
@@ -861,22 +859,17 @@ class CausalMaskedDiffWithXvec:
             klen_enc, klen_est = bf["klen_enc"], bf["klen_est"]
             klen_enc.fill_(Nv)
             klen_est.fill_(2 * Nv)
-        ews = self.encoder._workspace(B, N)
-        ops.embedding(self.emb_table, bf["idx"].view(-1), ews["tok"].view(B * N, cfg.enc_dim))
-        if stream_cache is not None and B == 1 and int(self.encoder.static_chunk_size) > 0 and N <= stream_cache.cap:
-            xa = self.encoder.forward_tokens_cached(stream_cache, ews["tok"], N, Nv, klen=klen_enc)
-        else:
-            self.encoder.forward_tokens(ews["tok"], B, N, klen=klen_enc, n_valid=Nv if padded else None)
-            xa = ews["b"]["xa"]
-        ops.linear(xa.view(B * T, cfg.enc_dim), self.proj_w, bias=self.proj_b, out_f32=ews["mu"].view(B * T, cfg.output_size))
         # conditions: prompt mel then zeros (flow.py:305-307)
         Tp = prompt_feats.shape[1]
         bf["cond"].zero_()
         bf["cond"][:, :Tp].copy_(prompt_feats.to(dev, torch.float32))
-        bf["x"].copy_(self.decoder._noise_cl[:T].unsqueeze(0).expand(B, -1, -1))
-        self.decoder.solve(bf["x"], ews["mu"], bf["spks"], bf["cond"], n_timesteps, klen=klen_est)
-        ops.to_channels_first(bf["x"], bf["mel"])
-        return bf["mel"][:, :, Tp:2 * Nv]
+
+        def encode(ews):
+            if stream_cache is not None and B == 1 and int(self.encoder.static_chunk_size) > 0 and N <= stream_cache.cap:
+                return self.encoder.forward_tokens_cached(stream_cache, ews["tok"], N, Nv, klen=klen_enc)
+            self.encoder.forward_tokens(ews["tok"], B, N, klen=klen_enc, n_valid=Nv if padded else None)
+            return ews["b"]["xa"]
+        return self._pass(bf, B, N, embeddings, encode, klen_est, n_timesteps)[:, :, Tp:2 * Nv]
 
     @torch.no_grad()
     def inference_ragged(self, tokens, prompt_tokens, prompt_feats, embeddings: torch.Tensor, n_timesteps: int = 10, padded: bool = False):
@@ -892,13 +885,7 @@ class CausalMaskedDiffWithXvec:
         nvs = [nps[b] + int(tokens[b].numel()) for b in range(B)]
         lb = int(getattr(self, "length_bucket", 0) or 0) or 1
         N = -(-max(nvs) // lb) * lb
-        T = 2 * N
-        D = embeddings.shape[1]
-        bf = self._buffers(B, N, D)
-        bf["emb_in"].copy_(embeddings.to(dev, torch.float32))
-        ops.layernorm(bf["emb_in"], None, None, 1e-24 / D, rms=True, out_scale=1.0 / math.sqrt(D), out_act=bf["emb_n"][:, :D])
-        ops.gemm(bf["emb_n"], self.spk_w, B, cfg.output_size, D, lda=bf["emb_n"].stride(0), bias=self.spk_b, out_f32=bf["spks"],
-                 ldo32=cfg.output_size)
+        bf = self._buffers(B, N, embeddings.shape[1])
         bf["idx"].fill_(-1)
         bf["cond"].zero_()
         for b in range(B):
@@ -909,26 +896,61 @@ class CausalMaskedDiffWithXvec:
         klen_enc, klen_est = bf["klen_enc"], bf["klen_est"]
         klen_enc.copy_(torch.tensor(nvs, dtype=torch.int32))
         klen_est.copy_(torch.tensor([2 * n for n in nvs], dtype=torch.int32))
-        ews = self.encoder._workspace(B, N)
-        ops.embedding(self.emb_table, bf["idx"].view(-1), ews["tok"].view(B * N, cfg.enc_dim))
-        self.encoder.forward_tokens(ews["tok"], B, N, klen=klen_enc, n_valid=nvs)
-        ops.linear(ews["b"]["xa"].view(B * T, cfg.enc_dim), self.proj_w, bias=self.proj_b, out_f32=ews["mu"].view(B * T, cfg.output_size))
-        bf["x"].copy_(self.decoder._noise_cl[:T].unsqueeze(0).expand(B, -1, -1))
-        self.decoder.solve(bf["x"], ews["mu"], bf["spks"], bf["cond"], n_timesteps, klen=klen_est)
-        ops.to_channels_first(bf["x"], bf["mel"])
+
+        def encode(ews):
+            self.encoder.forward_tokens(ews["tok"], B, N, klen=klen_enc, n_valid=nvs)
+            return ews["b"]["xa"]
+        mel = self._pass(bf, B, N, embeddings, encode, klen_est, n_timesteps)
         if padded:
             lens = [2 * (nvs[b] - nps[b]) for b in range(B)]
             out = torch.empty(B, cfg.output_size, max(lens), device=dev, dtype=torch.float32)
             for b in range(B):
-                out[b, :, :lens[b]].copy_(bf["mel"][b, :, 2 * nps[b]:2 * nvs[b]])
+                out[b, :, :lens[b]].copy_(mel[b, :, 2 * nps[b]:2 * nvs[b]])
             return out, lens
-        return [bf["mel"][b, :, 2 * nps[b]:2 * nvs[b]].clone() for b in range(B)]
+        return [mel[b, :, 2 * nps[b]:2 * nvs[b]].clone() for b in range(B)]
+
+    def _pass(self, bf, B, N, embeddings, encode, klen_est, n_timesteps):
+        """What ``inference_batch`` and ``inference_ragged`` share, over buffers whose ``idx`` / ``cond`` / klen the caller has filled:
+        speaker normalise + projection, token embedding, ``encode(encoder workspace) -> xa`` (the caller's encoder call),
+        encoder_proj = mu, the noise, the CFM solve.  Returns the whole channels-first mel (B, 80, 2N) of the buffer set."""
+        cfg, dev = self.cfg, self.device
+        T, D = 2 * N, embeddings.shape[1]
+        # speaker: F.normalize -> Linear (flow.py:286-287); RMSNorm kernel with scale 1/sqrt(D) == x / ||x||
+        bf["emb_in"].copy_(embeddings.to(dev, torch.float32))
+        ops.layernorm(bf["emb_in"], None, None, 1e-24 / D, rms=True, out_scale=1.0 / math.sqrt(D), out_act=bf["emb_n"][:, :D])
+        ops.gemm(bf["emb_n"], self.spk_w, B, cfg.output_size, D, lda=bf["emb_n"].stride(0), bias=self.spk_b, out_f32=bf["spks"],
+                 ldo32=cfg.output_size)
+        # tokens -> embedding -> encoder -> encoder_proj = mu (flow.py:290-302)
+        ews = self.encoder._workspace(B, N)
+        ops.embedding(self.emb_table, bf["idx"].view(-1), ews["tok"].view(B * N, cfg.enc_dim))
+        xa = encode(ews)
+        ops.linear(xa.view(B * T, cfg.enc_dim), self.proj_w, bias=self.proj_b, out_f32=ews["mu"].view(B * T, cfg.output_size))
+        bf["x"].copy_(self.decoder._noise_cl[:T].unsqueeze(0).expand(B, -1, -1))
+        self.decoder.solve(bf["x"], ews["mu"], bf["spks"], bf["cond"], n_timesteps, klen=klen_est)
+        ops.to_channels_first(bf["x"], bf["mel"])
+        return bf["mel"]
 
     supports_stream_cache = True
 
     def drop_stream_cache(self, cache_key):
         """End of a streaming request: release its encoder cache."""
-        self._stream_caches.pop(cache_key, None)
+        with self._stream_lock:
+            self._stream_caches.pop(cache_key, None)
+
+    def _stream_cache(self, cache_key, need):
+        """The encoder cache of a streaming request's chunk call with room for ``need`` tokens.  The first call of a request, or a request
+        that outgrew its cache, starts over with a larger one; room for it is made by evicting the least recently used requests —
+        never this one, and with ``stream_cache_cap`` >= the requests in flight never a live one, whose every chunk call renews it."""
+        with self._stream_lock:
+            ec = self._stream_caches.get(cache_key)
+            if ec is not None and ec.cap >= need:
+                self._stream_caches.move_to_end(cache_key)
+                return ec
+            self._stream_caches.pop(cache_key, None)
+            while len(self._stream_caches) >= max(1, int(self.stream_cache_cap)):
+                self._stream_caches.popitem(last=False)
+            ec = self._stream_caches[cache_key] = self.encoder.new_stream_cache(max(1024, _round_up(2 * need, 256)))
+            return ec
 
     @torch.no_grad()
     def inference(self, token, token_len, prompt_token, prompt_token_len, prompt_feat, prompt_feat_len, embedding,
@@ -945,12 +967,6 @@ class CausalMaskedDiffWithXvec:
             prompt_token = prompt_token[:, :int(prompt_token_len[0])]
         ec = None
         if cache_key is not None and self.stream_enc_cache and int(self.encoder.static_chunk_size) > 0:
-            need = int(prompt_token.shape[1] + token.shape[1]) + 64
-            ec = self._stream_caches.get(cache_key)
-            if ec is None or ec.cap < need:     # first call of the request, or the request outgrew its cache: start over, larger
-                while len(self._stream_caches) >= 8:
-                    self._stream_caches.pop(next(iter(self._stream_caches)))
-                ec = self.encoder.new_stream_cache(max(1024, _round_up(2 * need, 256)))
-                self._stream_caches[cache_key] = ec
+            ec = self._stream_cache(cache_key, int(prompt_token.shape[1] + token.shape[1]) + 64)
         mel = self.inference_batch(token, prompt_token, prompt_feat, embedding, n_timesteps, stream_cache=ec)
         return mel.float().clone(), None

@@ -377,19 +377,17 @@ class HiFTGenerator:
             up = self.ups[i]
             x32 = ws[f"x{i}"]
             off = 1 if last else 0
-            upf = 3 if ps else 0
-            for r, (wp, ntaps, cr, wps) in enumerate(up.phases):
-                ops.gemm(cur_a, wps.view(torch.float32) if ps else wp, t_in, c, ntaps * up.cin, batch=B, a_bs=(cur_a.stride(0), 0), lda=cur_a.stride(1),
+
+            def phase(r, M, row_off):   # M output rows of polyphase branch r from row row_off on, every up.u-th (the phase lambda of csrc/stages.hip)
+                wp, ntaps, cr, wps = up.phases[r]
+                ops.gemm(cur_a, wps.view(torch.float32) if ps else wp, M, c, ntaps * up.cin, batch=B, a_bs=(cur_a.stride(0), 0), lda=cur_a.stride(1),
                          a_rows=t_in, cin=up.cin, tap_base=cr, tap_step=-1, bias=up.b, res=si1,
                          res_bs=(si1.stride(0), 0), ldres=c, out_f32=x32, o32_bs=(x32.stride(0), 0), ldo32=c,
-                         out_row_stride=up.u, out_row_off=r + off, out_rows=t_out, x3_flags=upf, ldw=ntaps * up.cin)
+                         out_row_stride=up.u, out_row_off=row_off, out_rows=t_out, x3_flags=3 if ps else 0, ldw=ntaps * up.cin)
+            for r in range(len(up.phases)):
+                phase(r, t_in, r + off)
             if last:
-                # ReflectionPad1d((1,0)): padded[0] = ups_out[1] = phase r=1, q=0
-                wp, ntaps, cr, wps = up.phases[1]
-                ops.gemm(cur_a, wps.view(torch.float32) if ps else wp, 1, c, ntaps * up.cin, batch=B, a_bs=(cur_a.stride(0), 0), lda=cur_a.stride(1),
-                         a_rows=t_in, cin=up.cin, tap_base=cr, tap_step=-1, bias=up.b, res=si1,
-                         res_bs=(si1.stride(0), 0), ldres=c, out_f32=x32, o32_bs=(x32.stride(0), 0), ldo32=c,
-                         out_row_stride=up.u, out_row_off=0, out_rows=t_out, x3_flags=upf, ldw=ntaps * up.cin)
+                phase(1, 1, 0)   # ReflectionPad1d((1,0)): padded[0] = ups_out[1] = phase r=1, q=0
             # parallel ResBlocks, mean over kernels (generator.py:366-372)
             rbs = self.resblocks[i * nk:(i + 1) * nk]
             xas = ws[f"xa{i}"]

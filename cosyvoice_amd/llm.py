@@ -13,6 +13,7 @@ Design (MI355X-first, not the reference's 4-graphs-per-layer path, llm/qwen2_5.p
   * weights: 16-bit, pre-packed at load into MFMA B-fragment order for the decode path (1 KiB per wave-load).
 Batching: B <= 16 sequences per step share every weight read (the reference is batch-1).
 """
+import contextlib
 import copy
 import math
 from typing import Dict, Generator, List, Optional, Union
@@ -149,12 +150,14 @@ class Qwen2LM:
         self._vt_rm = z(MB, cfg.num_kv_heads, 64, self.ctx_max, dtype=dt)
 
     # ------------------------------------------------------------------ decode step (graph-capturable)
-    def _head_and_sample(self, B, use_forced, use_uniforms):
+    def _head_and_sample(self, B, use_forced, use_uniforms, lora=False):
         cfg, st = self.cfg, self.st
-        H = cfg.hidden_size
-        ops.skinny_gemm(st["xn"], self.p_dec, B, cfg.out_vocab, H, bias=self.dec_b, out_f32=st["logits"], ldo=self.Vpad,
+        ops.skinny_gemm(st["xn"], self.p_dec, B, cfg.out_vocab, cfg.hidden_size, bias=self.dec_b, out_f32=st["logits"], ldo=self.Vpad,
                         max_wgs=2 * self.cu_budget)
-        ops.sample_ras(self._sample_params(B, use_forced, use_uniforms))
+        if lora:
+            bank = self._lora["bank"]
+            self._lora_delta(st["xn"], bank.A_dec, bank.B_dec, st["logits"], B)
+        ops.sample_ras(self._sample_params(B, use_forced, use_uniforms))   # writes the BASE speech_embedding row as the next input (llm.py:874)
 
     def _sample_params(self, B, use_forced, use_uniforms):
         cfg, st = self.cfg, self.st
@@ -221,46 +224,53 @@ class Qwen2LM:
         else:
             self.st["nonce"].copy_(torch.tensor([int(nonce) * 0x9E3779B97F4A7C15 % (2 ** 62), 0], dtype=torch.int64))
 
-    def _decode_step(self, B, use_forced=False, use_uniforms=False):
+    def _decode_step(self, B, use_forced=False, use_uniforms=False, lora=False):
+        """One token for B rows.  Three forms around the same launches:
+          * fused prologue (up to 8 rows): the QKV kernel sums the previous layer's down-proj slabs into the residual and normalises it
+            itself; the residual ping-pongs between x (even layers) and x2 (odd): the prologue reads one and its workgroup (0,0) writes
+            the summed residual to the other;
+          * split QKV norm (more than 8 rows, _split_qkv): the fused prologue (each of the QKV kernel's 72 workgroups re-reads the fp32
+            residual + KS slabs of every row: 286 KB at 16 rows) costs more than a launch — one workgroup per row sums the slabs into
+            the residual and leaves the normalised 16-bit row (cv_rmsnorm_reduce), the QKV kernel streams plain rows (16 rows on the
+            decode loops' 64 CUs: 10.7 -> 3.4 + 4.3 us, tools/llm_kernel_bench.py); the residual is updated in place, no ping-pong;
+          * ``lora``: the low-rank terms spliced in between the base kernels, each row with row_adapter[row].  Always split (the
+            normalised rows must exist in memory for the shrink), the gate/up pre-activations in fp32 (+LoRA, then SwiGLU), and the
+            down-proj term as one more slab."""
         cfg, st = self.cfg, self.st
         H, I = cfg.hidden_size, cfg.intermediate_size
         qkv_dim = cfg.q_dim + 2 * cfg.kv_dim
         KS = self.DOWN_KSPLIT
         scale = 1.0 / math.sqrt(cfg.head_dim)
         mw = self.cu_budget
-        if self._split_qkv(B):
-            # more than 8 rows: the QKV kernel's fused prologue (each of its 72 workgroups re-reads the fp32 residual + KS slabs of
-            # every row: 286 KB at 16 rows) costs more than a launch — one workgroup per row sums the slabs into the residual and
-            # leaves the normalised 16-bit row (cv_rmsnorm_reduce), the QKV kernel streams plain rows (16 rows on the decode loops'
-            # 64 CUs: 10.7 -> 3.4 + 4.3 us, tools/llm_kernel_bench.py); the residual is then updated in place, no ping-pong
-            x = st["x"]
-            for li, lay in enumerate(self.layers):
-                if li > 0:
-                    ops.rmsnorm_reduce(x, lay["g_in"], cfg.rms_eps, st["xn"], B, slabs=st["slabs"], nslab=KS, slab_stride=self._rp(B) * H, ld_slab=H)
-                else:
-                    ops.rmsnorm_reduce(x, lay["g_in"], cfg.rms_eps, st["xn"], B)
-                ops.skinny_gemm(st["xn"], lay["p_qkv"], B, qkv_dim, H, bias=lay["bqkv"], out_f32=st["qkv"], ldo=qkv_dim)
-                ops.decode_attention(st["q"], self.kcache[li], self.vtcache[li], st["pos"], 1, st["ao"], B, cfg.num_heads,
-                                     cfg.num_kv_heads, self.ctx_max, scale, qkv=st["qkv"], inv_freq=self.rope_table)
-                ops.skinny_gemm(st["ao"], lay["p_o"], B, H, cfg.q_dim, mode=1, out_f32=x, ldo=H,
-                                split_out=dict(xb=st["xb"], ss=st["ssp"]))
-                ops.skinny_gemm(st["xb"], lay["p_gu_g"], B, 2 * I, H, mode=2, out_act=st["h"], ldoa=I,
-                                split_in=dict(rs=st["ssp"], n=st["ssp"].shape[0], eps=cfg.rms_eps))
-                ops.skinny_gemm(st["h"], lay["p_down"], B, H, I, ksplit=KS, out_f32=st["slabs"], ldo=H, slab_stride=self._rp(B) * H, max_wgs=mw)
-            ops.rmsnorm_reduce(x, self.g_final, cfg.rms_eps, st["xn"], B, slabs=st["slabs"], nslab=KS, slab_stride=self._rp(B) * H, ld_slab=H)
-            self._head_and_sample(B, use_forced, use_uniforms)
-            return
-        # residual stream ping-pongs between x (even layers) and x2 (odd): the fused prologue of the QKV kernel reads
-        # cur (+ the previous layer's down-proj slabs) and its workgroup (0,0) writes the summed residual to nxt
-        cur, nxt = st["x"], st["x2"]
+        split = lora or self._split_qkv(B)
+        slabs, ss = st["slabs"], self._rp(B) * H
+        pending = dict(slabs=slabs, nslab=KS, slab_stride=ss, ld_slab=H)     # the down-proj slabs not yet summed into the residual
+        if lora:
+            lo = self._lora
+            bank, slabs = lo["bank"], lo["slabs"]
+            plane = slabs.view(-1)[KS * ss:KS * ss + B * H].view(B, H)      # the LoRA slab of down_proj
+            pending.update(slabs=slabs, nslab=KS + 1)
+        cur, nxt = st["x"], (st["x"] if split else st["x2"])     # the residual a layer reads / leaves updated (split: in place)
+        if split:
+            ops.rmsnorm_reduce(cur, self.layers[0]["g_in"], cfg.rms_eps, st["xn"], B)
         for li, lay in enumerate(self.layers):
-            nrm = dict(x=cur, gamma=lay["g_in"], eps=cfg.rms_eps, x_out=nxt)
-            if li > 0:
-                nrm.update(slabs=st["slabs"], nslab=KS, slab_stride=self._rp(B) * H, ld_slab=H)
-            ops.skinny_gemm(st["xn"], lay["p_qkv"], B, qkv_dim, H, bias=lay["bqkv"], out_f32=st["qkv"], ldo=qkv_dim, norm=nrm)
+            lb = bank.layers[li] if lora else None
+            if split:
+                ops.skinny_gemm(st["xn"], lay["p_qkv"], B, qkv_dim, H, bias=lay["bqkv"], out_f32=st["qkv"], ldo=qkv_dim)
+            else:
+                nrm = dict(x=cur, gamma=lay["g_in"], eps=cfg.rms_eps, x_out=nxt, **(pending if li > 0 else {}))
+                ops.skinny_gemm(st["xn"], lay["p_qkv"], B, qkv_dim, H, bias=lay["bqkv"], out_f32=st["qkv"], ldo=qkv_dim, norm=nrm)
+            if lora:
+                self._lora_delta(st["xn"], lb["A_qkv"], lb["B_qkv"], st["qkv"], B, segments=bank.qkv_segments)
             ops.decode_attention(st["q"], self.kcache[li], self.vtcache[li], st["pos"], 1, st["ao"], B, cfg.num_heads,
                                  cfg.num_kv_heads, self.ctx_max, scale, qkv=st["qkv"], inv_freq=self.rope_table)
-            if self.split_norm:
+            if lora:
+                ops.skinny_gemm(st["ao"], lay["p_o"], B, H, cfg.q_dim, mode=1, out_f32=nxt, ldo=H)
+                self._lora_delta(st["ao"], lb["A_o"], lb["B_o"], nxt, B)
+                ops.rmsnorm_reduce(nxt, lay["g_post"], cfg.rms_eps, st["xn"], B)
+                ops.skinny_gemm(st["xn"], lay["p_gu"], B, 2 * I, H, out_f32=lo["gu"], ldo=2 * I)
+                self._lora_delta(st["xn"], lb["A_gu"], lb["B_gu"], lo["gu"], B, mode=L.LORA_SWIGLU, segments=bank.gu_segments, h=st["h"])
+            elif self.split_norm:
                 # post-attention RMSNorm split over the two launches: o_proj also leaves the updated rows as 16-bit and its
                 # workgroups' partial sums of squares; gate/up reads those rows straight into MFMA fragments (no prologue, no
                 # LDS image, no barrier) and applies 1/rms in its epilogue (gamma is folded into the packed weights)
@@ -272,10 +282,15 @@ class Qwen2LM:
                 ops.skinny_gemm(st["ao"], lay["p_o"], B, H, cfg.q_dim, mode=1, out_f32=nxt, ldo=H)
                 ops.skinny_gemm(st["xn"], lay["p_gu"], B, 2 * I, H, mode=2, out_act=st["h"], ldoa=I,
                                 norm=dict(x=nxt, gamma=lay["g_post"], eps=cfg.rms_eps), max_wgs=mw)
-            ops.skinny_gemm(st["h"], lay["p_down"], B, H, I, ksplit=KS, out_f32=st["slabs"], ldo=H, slab_stride=self._rp(B) * H, max_wgs=mw)
+            ops.skinny_gemm(st["h"], lay["p_down"], B, H, I, ksplit=KS, out_f32=slabs, ldo=H, slab_stride=ss, max_wgs=mw)
+            if lora:
+                self._lora_delta(st["h"], lb["A_down"], lb["B_down"], plane, B, mode=L.LORA_STORE)
             cur, nxt = nxt, cur
-        ops.rmsnorm_reduce(cur, self.g_final, cfg.rms_eps, st["xn"], B, slabs=st["slabs"], nslab=KS, slab_stride=self._rp(B) * H, ld_slab=H)
-        self._head_and_sample(B, use_forced, use_uniforms)
+            last = li + 1 == len(self.layers)
+            if split or last:      # residual += slabs, normalised for the next reader: the next layer's plain QKV kernel, or the head
+                gamma = self.g_final if last else self.layers[li + 1]["g_in"]
+                ops.rmsnorm_reduce(cur, gamma, cfg.rms_eps, st["xn"], B, **pending)
+        self._head_and_sample(B, use_forced, use_uniforms, lora)
 
     # ------------------------------------------------------------------ per-sequence LoRA (cosyvoice_amd/lora.py)
     def attach_lora(self, bank):
@@ -325,58 +340,6 @@ class Qwen2LM:
         ops.lora_shrink(x, A, lo["row_adapter"], u, rows, rps)
         ops.lora_expand(u, B_, lo["bank"].s, lo["row_adapter"], y, rows, rps, mode=mode, segments=segments, h=h, ldy=ldy)
 
-    def _head_and_sample_lora(self, B, use_forced, use_uniforms):
-        cfg, st, bank = self.cfg, self.st, self._lora["bank"]
-        ops.skinny_gemm(st["xn"], self.p_dec, B, cfg.out_vocab, cfg.hidden_size, bias=self.dec_b, out_f32=st["logits"], ldo=self.Vpad,
-                        max_wgs=2 * self.cu_budget)
-        self._lora_delta(st["xn"], bank.A_dec, bank.B_dec, st["logits"], B)
-        ops.sample_ras(self._sample_params(B, use_forced, use_uniforms))   # writes the BASE speech_embedding row (llm.py:874)
-
-    def _decode_step_lora(self, B, use_forced=False, use_uniforms=False):
-        """The decode step with the low-rank terms spliced in between the base kernels, each row with row_adapter[row].  Always the
-        split form (the normalised rows must exist in memory for the shrink): per layer rmsnorm_reduce -> QKV -> +LoRA -> attention ->
-        o_proj (in-place residual) -> +LoRA -> rmsnorm -> gate/up pre-activations (fp32) -> +LoRA, SwiGLU -> down split-K slabs ->
-        LoRA as one more slab."""
-        cfg, st, lo = self.cfg, self.st, self._lora
-        bank = lo["bank"]
-        H, I = cfg.hidden_size, cfg.intermediate_size
-        qkv_dim = cfg.q_dim + 2 * cfg.kv_dim
-        KS = self.DOWN_KSPLIT
-        scale = 1.0 / math.sqrt(cfg.head_dim)
-        ss = self._rp(B) * H
-        slabs = lo["slabs"]
-        plane = slabs.view(-1)[KS * ss:KS * ss + B * H].view(B, H)      # the LoRA slab of down_proj
-        x = st["x"]
-        for li, (lay, lb) in enumerate(zip(self.layers, bank.layers)):
-            if li > 0:
-                ops.rmsnorm_reduce(x, lay["g_in"], cfg.rms_eps, st["xn"], B, slabs=slabs, nslab=KS + 1, slab_stride=ss, ld_slab=H)
-            else:
-                ops.rmsnorm_reduce(x, lay["g_in"], cfg.rms_eps, st["xn"], B)
-            ops.skinny_gemm(st["xn"], lay["p_qkv"], B, qkv_dim, H, bias=lay["bqkv"], out_f32=st["qkv"], ldo=qkv_dim)
-            self._lora_delta(st["xn"], lb["A_qkv"], lb["B_qkv"], st["qkv"], B, segments=bank.qkv_segments)
-            ops.decode_attention(st["q"], self.kcache[li], self.vtcache[li], st["pos"], 1, st["ao"], B, cfg.num_heads,
-                                 cfg.num_kv_heads, self.ctx_max, scale, qkv=st["qkv"], inv_freq=self.rope_table)
-            ops.skinny_gemm(st["ao"], lay["p_o"], B, H, cfg.q_dim, mode=1, out_f32=x, ldo=H)
-            self._lora_delta(st["ao"], lb["A_o"], lb["B_o"], x, B)
-            ops.rmsnorm_reduce(x, lay["g_post"], cfg.rms_eps, st["xn"], B)
-            ops.skinny_gemm(st["xn"], lay["p_gu"], B, 2 * I, H, out_f32=lo["gu"], ldo=2 * I)
-            self._lora_delta(st["xn"], lb["A_gu"], lb["B_gu"], lo["gu"], B, mode=L.LORA_SWIGLU, segments=bank.gu_segments, h=st["h"])
-            ops.skinny_gemm(st["h"], lay["p_down"], B, H, I, ksplit=KS, out_f32=slabs, ldo=H, slab_stride=ss, max_wgs=self.cu_budget)
-            self._lora_delta(st["h"], lb["A_down"], lb["B_down"], plane, B, mode=L.LORA_STORE)
-        ops.rmsnorm_reduce(x, self.g_final, cfg.rms_eps, st["xn"], B, slabs=slabs, nslab=KS + 1, slab_stride=ss, ld_slab=H)
-        self._head_and_sample_lora(B, use_forced, use_uniforms)
-
-    def _step_lora(self, B, use_forced, use_uniforms):
-        if not self.use_graph:
-            self._decode_step_lora(B, use_forced, use_uniforms)
-            return
-        key = self._graph_key(B, use_forced, use_uniforms) + ("lora", id(self._lora["bank"]))
-        g = self._graphs.get(key)
-        if g is None:
-            g = ops.Graph().capture(lambda: self._decode_step_lora(B, use_forced, use_uniforms))
-            self._graphs[key] = g
-        g.launch()
-
     def _lora_workspace(self, B, Lp):
         lo = self._lora
         key = (B, Lp)
@@ -386,48 +349,6 @@ class Qwen2LM:
             e = lambda *s: torch.empty(*s, device=self.device, dtype=torch.float32)
             lo["ws"][key] = dict(u=e(rows, 3 * lo["bank"].r), gu=e(rows, 2 * self.cfg.intermediate_size))
         return lo["ws"][key]
-
-    def _prefill_lora(self, B, Lp, use_forced, use_uniforms, lens=None):
-        """_prefill with the low-rank terms spliced around the same GEMMs over the B * Lp rows (row_adapter[row // Lp])."""
-        cfg, dev, st, lo = self.cfg, self.device, self.st, self._lora
-        bank = lo["bank"]
-        H = cfg.hidden_size
-        ws, lw = self._prefill_workspace(B, Lp), self._lora_workspace(B, Lp)
-        rows = B * Lp
-        x, u = ws["x"], lw["u"]
-        st["pos"].zero_()
-        scale = 1.0 / math.sqrt(cfg.head_dim)
-        klen = None
-        if lens is not None and any(l != Lp for l in lens):
-            klen = torch.tensor(list(lens), dtype=torch.int32, device=dev)
-        for li, (lay, lb) in enumerate(zip(self.layers, bank.layers)):
-            ops.layernorm(x, lay["g_in"], None, cfg.rms_eps, rms=True, out_act=ws["xn"])
-            ops.linear(ws["xn"], lay["wqkv"], bias=lay["bqkv"], out_f32=ws["qkv"])
-            self._lora_delta(ws["xn"], lb["A_qkv"], lb["B_qkv"], ws["qkv"], rows, Lp, segments=bank.qkv_segments, u=u)
-            ops.rope_append(ws["qkv"], st["pos"], rows, Lp, cfg.num_heads, cfg.num_kv_heads, self.inv_freq, ws["q"], self._k_rm,
-                            self._vt_rm, self.ctx_max)
-            ops.attention(ws["q"], self._k_rm, self._vt_rm, ws["ao"], B=B, H=cfg.num_heads, Hkv=cfg.num_kv_heads, Tq=Lp,
-                          Tk=Lp, scale=scale, q_bs=Lp * cfg.q_dim, ldq=cfg.q_dim, k_bs=cfg.num_kv_heads * self.ctx_max * 64,
-                          k_hs=self.ctx_max * 64, ldk=64, vt_ld=self.ctx_max, o_bs=Lp * cfg.q_dim, ldo=cfg.q_dim, causal=True,
-                          klen=klen)
-            ops.kv_retile(self._k_rm, self._vt_rm, self.kcache[li], self.vtcache[li], B, cfg.num_kv_heads, self.ctx_max, Lp)
-            ops.linear(ws["ao"], lay["wo"], res=x, out_f32=x)
-            self._lora_delta(ws["ao"], lb["A_o"], lb["B_o"], x, rows, Lp, u=u)
-            ops.layernorm(x, lay["g_post"], None, cfg.rms_eps, rms=True, out_act=ws["xn"])
-            ops.linear(ws["xn"], lay["wgu"], out_f32=lw["gu"])      # the [gate16 | up16] pre-activations, no epilogue
-            self._lora_delta(ws["xn"], lb["A_gu"], lb["B_gu"], lw["gu"], rows, Lp, mode=L.LORA_SWIGLU, segments=bank.gu_segments,
-                             h=ws["h"], u=u)
-            ops.linear(ws["h"], lay["wdown"], res=x, out_f32=x)
-            self._lora_delta(ws["h"], lb["A_down"], lb["B_down"], x, rows, Lp, u=u)
-        if klen is None:
-            st["x"][:B].copy_(x.view(B, Lp, H)[:, Lp - 1])
-            st["pos"][:B].fill_(Lp - 1)
-        else:
-            last = (klen - 1).long()
-            st["x"][:B].copy_(x.view(B, Lp, H)[torch.arange(B, device=dev), last])
-            st["pos"][:B].copy_(klen - 1)
-        ops.rmsnorm_reduce(st["x"], self.g_final, cfg.rms_eps, st["xn"], B)
-        self._head_and_sample_lora(B, use_forced, use_uniforms)
 
     def _assemble_lora(self, ws, texts, prompt_texts, prompt_speech, B, Lp):
         """The adapted rows of the prefill assembly (llm.py:840,849): embed_tokens(text) and speech_embedding(prompt speech) are module
@@ -454,43 +375,51 @@ class Qwen2LM:
         return (B, use_forced, use_uniforms, self.seed, self.cu_budget, self.top_p, self.top_k, self.fallback_mode, self.top_p2, self.top_k2,
                 self.split_norm, self.use_stage_abi, bool(self._split_qkv(B)))
 
-    def _step(self, B, use_forced, use_uniforms):
+    def _step(self, B, use_forced, use_uniforms, lora=False):
         if not self.use_graph:
-            self._decode_step(B, use_forced, use_uniforms)
+            self._decode_step(B, use_forced, use_uniforms, lora)
             return
         key = self._graph_key(B, use_forced, use_uniforms)
+        if lora:
+            key += ("lora", id(self._lora["bank"]))   # detach_lora drops the graphs with this suffix
         g = self._graphs.get(key)
         if g is None:
-            if self.use_stage_abi and self.split_norm and self.cu_budget == 0:
+            if not lora and self.use_stage_abi and self.split_norm and self.cu_budget == 0:
                 # the whole step composed and captured inside the library (cv_llm_step_graph_create): same launches as
                 # _decode_step, which stays as the eager path and as the cross-check of the C composition (tests)
                 g = ops.Graph.from_llm_step(self._step_desc(B, use_forced, use_uniforms))
             else:
-                g = ops.Graph().capture(lambda: self._decode_step(B, use_forced, use_uniforms))
+                g = ops.Graph().capture(lambda: self._decode_step(B, use_forced, use_uniforms, lora))
             self._graphs[key] = g
         g.launch()
 
     # ------------------------------------------------------------------ prefill
-    def _prefill(self, B, Lp, use_forced, use_uniforms, lens=None):
+    def _prefill(self, B, Lp, use_forced, use_uniforms, lens=None, lora=False):
         """Input embeddings already in ws['x'] (B*Lp, H) fp32.  Writes the KV caches for positions [0,Lp), leaves the
         last position's hidden state in st['x'] and runs head + sampling (llm.py:861-866, first loop iteration).
         ``lens`` (list of B ints <= Lp): ragged batch, sequence b occupies rows [0, lens[b]) of its Lp-row slot (the rest are
         zero embeddings): attention is limited to its own keys, its decode state starts at lens[b]; the cache entries the
-        padded rows write beyond lens[b] are never read (decode attends to ctx_len keys) and get overwritten as b grows."""
-        cfg, dt, dev, st = self.cfg, self.dtype, self.device, self.st
-        H, I = cfg.hidden_size, cfg.intermediate_size
-        qkv_dim = cfg.q_dim + 2 * cfg.kv_dim
+        padded rows write beyond lens[b] are never read (decode attends to ctx_len keys) and get overwritten as b grows.
+        ``lora``: the low-rank terms spliced around the same GEMMs over the B * Lp rows (row_adapter[row // Lp])."""
+        cfg, dev, st = self.cfg, self.device, self.st
+        H = cfg.hidden_size
         ws = self._prefill_workspace(B, Lp)
         rows = B * Lp
         x = ws["x"]
+        if lora:
+            bank, lw = self._lora["bank"], self._lora_workspace(B, Lp)
+            delta = lambda a, lb, w, y, **kw: self._lora_delta(a, lb["A_" + w], lb["B_" + w], y, rows, Lp, u=lw["u"], **kw)
         st["pos"].zero_()
         scale = 1.0 / math.sqrt(cfg.head_dim)
         klen = None
         if lens is not None and any(l != Lp for l in lens):
             klen = torch.tensor(list(lens), dtype=torch.int32, device=dev)
         for li, lay in enumerate(self.layers):
+            lb = bank.layers[li] if lora else None
             ops.layernorm(x, lay["g_in"], None, cfg.rms_eps, rms=True, out_act=ws["xn"])
             ops.linear(ws["xn"], lay["wqkv"], bias=lay["bqkv"], out_f32=ws["qkv"])
+            if lora:
+                delta(ws["xn"], lb, "qkv", ws["qkv"], segments=bank.qkv_segments)
             ops.rope_append(ws["qkv"], st["pos"], rows, Lp, cfg.num_heads, cfg.num_kv_heads, self.inv_freq, ws["q"], self._k_rm,
                             self._vt_rm, self.ctx_max)
             ops.attention(ws["q"], self._k_rm, self._vt_rm, ws["ao"], B=B, H=cfg.num_heads, Hkv=cfg.num_kv_heads, Tq=Lp,
@@ -499,9 +428,17 @@ class Qwen2LM:
                           klen=klen)
             ops.kv_retile(self._k_rm, self._vt_rm, self.kcache[li], self.vtcache[li], B, cfg.num_kv_heads, self.ctx_max, Lp)
             ops.linear(ws["ao"], lay["wo"], res=x, out_f32=x)
+            if lora:
+                delta(ws["ao"], lb, "o", x)
             ops.layernorm(x, lay["g_post"], None, cfg.rms_eps, rms=True, out_act=ws["xn"])
-            ops.linear(ws["xn"], lay["wgu"], act=ops.ACT_SWIGLU, out_act=ws["h"])
+            if lora:
+                ops.linear(ws["xn"], lay["wgu"], out_f32=lw["gu"])      # the [gate16 | up16] pre-activations, no epilogue
+                delta(ws["xn"], lb, "gu", lw["gu"], mode=L.LORA_SWIGLU, segments=bank.gu_segments, h=ws["h"])
+            else:
+                ops.linear(ws["xn"], lay["wgu"], act=ops.ACT_SWIGLU, out_act=ws["h"])
             ops.linear(ws["h"], lay["wdown"], res=x, out_f32=x)
+            if lora:
+                delta(ws["h"], lb, "down", x)
         # last position of every sequence -> decode state
         if klen is None:
             st["x"][:B].copy_(x.view(B, Lp, H)[:, Lp - 1])
@@ -511,7 +448,7 @@ class Qwen2LM:
             st["x"][:B].copy_(x.view(B, Lp, H)[torch.arange(B, device=dev), last])
             st["pos"][:B].copy_(klen - 1)
         ops.rmsnorm_reduce(st["x"], self.g_final, cfg.rms_eps, st["xn"], B)
-        self._head_and_sample(B, use_forced, use_uniforms)
+        self._head_and_sample(B, use_forced, use_uniforms, lora)
 
     def _prefill_workspace(self, B, Lp):
         key = (B, Lp)
@@ -553,6 +490,35 @@ class Qwen2LM:
         for b, e in enumerate(lm_inputs):
             x[b, :e.shape[0]].copy_(e.to(self.device, torch.float32))
 
+    def _reset_request(self, B, forced=None):
+        """Request state of a new run over B rows: counters zeroed, the rows beyond B finished; ``forced`` (per row a token list):
+        the teacher-forced prefix of every row (-2 = past its end)."""
+        st = self.st
+        for k in ("step", "n_emitted", "finished"):
+            st[k].zero_()
+        st["finished"][B:].fill_(1)
+        if forced is not None:
+            f = torch.full((self.R, self.max_out), -2, dtype=torch.int32)
+            for b in range(B):
+                f[b, :len(forced[b])] = torch.tensor(forced[b], dtype=torch.int32)
+            st["forced"].copy_(f)
+
+    def _start(self, texts, prompt_texts, prompt_speech, B, Lp, use_forced, use_uniforms, lens=None, lm_inputs=None, lora=False,
+               prefill_stream=None):
+        """Assemble the B input sequences and prefill them (first token included), on ``prefill_stream`` when one is given."""
+        ws = self._prefill_workspace(B, Lp)
+        side = prefill_stream is not None
+        if side:
+            cur = torch.cuda.current_stream()
+            prefill_stream.wait_stream(cur)            # the state resets of the request
+        with torch.cuda.stream(prefill_stream) if side else contextlib.nullcontext():
+            self._assemble(ws, texts, prompt_texts, prompt_speech, B, Lp, lm_inputs)
+            if lora and lm_inputs is None:
+                self._assemble_lora(ws, texts, prompt_texts, prompt_speech, B, Lp)
+            self._prefill(B, Lp, use_forced, use_uniforms, lens, lora)
+        if side:
+            cur.wait_stream(prefill_stream)            # KV caches, first token and decode state are in place
+
     # ------------------------------------------------------------------ public API
     @torch.no_grad()
     def generate_batch(self, texts: List[torch.Tensor], prompt_texts: List[torch.Tensor], prompt_speech: List[torch.Tensor],
@@ -576,18 +542,14 @@ class Qwen2LM:
         assert 1 <= B <= self.max_batch
         st = self.st
         lora = self._set_adapters(adapters, B)
-        prefill = self._prefill_lora if lora else self._prefill
-        step = self._step_lora if lora else self._step
         if lm_inputs is not None:
             assert len(lm_inputs) == B and all(e.dim() == 2 and e.shape[1] == self.cfg.hidden_size for e in lm_inputs)
             lens = [int(e.shape[0]) for e in lm_inputs]
         else:
             lens = [1 + prompt_texts[b].numel() + texts[b].numel() + 1 + prompt_speech[b].numel() for b in range(B)]
         Lp = max(lens)   # ragged batches are left-aligned in Lp-row slots
-        ws = self._prefill_workspace(B, Lp)
-        for k in ("step", "n_emitted", "finished"):
-            st[k].zero_()
-        st["finished"][B:].fill_(1)
+        use_forced = forced is not None
+        self._reset_request(B, forced)
         mn = torch.zeros(self.R, dtype=torch.int32)
         mx = torch.zeros(self.R, dtype=torch.int32)
         for b in range(B):
@@ -597,37 +559,18 @@ class Qwen2LM:
             assert lens[b] + int(mx[b]) <= self.ctx_max and Lp <= self.ctx_max, "ctx_max too small"
         st["min_len"].copy_(mn)
         st["max_len"].copy_(mx)
-        use_forced = forced is not None
-        if use_forced:
-            f = torch.full((self.R, self.max_out), -2, dtype=torch.int32)
-            for b in range(B):
-                f[b, :len(forced[b])] = torch.tensor(forced[b], dtype=torch.int32)
-            st["forced"].copy_(f)
         use_uniforms = uniforms is not None
         if use_uniforms:
             st["uniforms"].copy_(uniforms.to(torch.float32))
         else:
             self._new_request_nonce()
-        if prefill_stream is not None:
-            cur = torch.cuda.current_stream()
-            prefill_stream.wait_stream(cur)            # the state resets above
-            with torch.cuda.stream(prefill_stream):
-                self._assemble(ws, texts, prompt_texts, prompt_speech, B, Lp, lm_inputs)
-                if lora and lm_inputs is None:
-                    self._assemble_lora(ws, texts, prompt_texts, prompt_speech, B, Lp)
-                prefill(B, Lp, use_forced, use_uniforms, lens)
-            cur.wait_stream(prefill_stream)            # KV caches, first token and decode state are in place
-        else:
-            self._assemble(ws, texts, prompt_texts, prompt_speech, B, Lp, lm_inputs)
-            if lora and lm_inputs is None:
-                self._assemble_lora(ws, texts, prompt_texts, prompt_speech, B, Lp)
-            prefill(B, Lp, use_forced, use_uniforms, lens)
+        self._start(texts, prompt_texts, prompt_speech, B, Lp, use_forced, use_uniforms, lens, lm_inputs, lora, prefill_stream)
         limit = int(mx[:B].max()) if max_steps is None else max_steps
         done_steps = 1
         while done_steps < limit:
             n = min(steps_per_poll, limit - done_steps)
             for _ in range(n):
-                step(B, use_forced, use_uniforms)
+                self._step(B, use_forced, use_uniforms, lora)
             done_steps += n
             if bool((st["finished"][:B] != 0).all().item()):
                 break
@@ -652,10 +595,7 @@ class Qwen2LM:
         st = self.st
         B = 1
         Lp = int(lm_input.shape[0]) if lm_input is not None else 1 + prompt_text.numel() + text.numel() + 1 + prompt_speech_token.numel()
-        ws = self._prefill_workspace(B, Lp)
-        for k in ("step", "n_emitted", "finished"):
-            st[k].zero_()
-        st["finished"][B:].fill_(1)
+        self._reset_request(B)
         tl = text.numel()
         min_len, max_len = int(tl * min_token_text_ratio), int(tl * max_token_text_ratio)
         if Lp + max_len > self.ctx_max:
@@ -663,10 +603,8 @@ class Qwen2LM:
         st["min_len"].fill_(min_len)
         st["max_len"].fill_(max_len)
         self._new_request_nonce(nonce)
-        self._assemble(ws, [text], [prompt_text], [prompt_speech_token], B, Lp, None if lm_input is None else [lm_input])
-        if lora and lm_input is None:
-            self._assemble_lora(ws, [text], [prompt_text], [prompt_speech_token], B, Lp)
-        (self._prefill_lora if lora else self._prefill)(B, Lp, False, False)
+        self._start([text], [prompt_text], [prompt_speech_token], B, Lp, False, False,
+                    lm_inputs=None if lm_input is None else [lm_input], lora=lora)
         sent, steps = 0, 1
         while True:
             fin = int(st["finished"][0].item())
@@ -681,7 +619,7 @@ class Qwen2LM:
                 break
             n = min(8, max_len - steps)
             for _ in range(n):
-                (self._step_lora if lora else self._step)(B, False, False)
+                self._step(B, False, False, lora)
             steps += n
 
     # teacher-forced log-probs for parity tests (not on the product path of tts())
@@ -698,25 +636,16 @@ class Qwen2LM:
         assert 1 <= B <= self.max_batch and len(forced) + 1 <= self.max_out
         Lp = 1 + prompt_text.numel() + text.numel() + 1 + prompt_speech.numel()
         assert Lp + len(forced) + 1 <= self.ctx_max, "ctx_max too small"
-        ws = self._prefill_workspace(B, Lp)
-        for k in ("step", "n_emitted", "finished"):
-            st[k].zero_()
-        st["finished"][B:].fill_(1)
+        self._reset_request(B, [forced] * B)
         st["min_len"].fill_(0)
         st["max_len"].fill_(len(forced) + 8)
-        f = torch.full((self.R, self.max_out), -2, dtype=torch.int32)
-        f[:B, :len(forced)] = torch.tensor(forced, dtype=torch.int32)
-        st["forced"].copy_(f)
-        self._assemble_inputs(ws, [text] * B, [prompt_text] * B, [prompt_speech] * B, B, Lp)
-        if lora:
-            self._assemble_lora(ws, [text] * B, [prompt_text] * B, [prompt_speech] * B, B, Lp)
         want = set(range(len(forced) + 1)) if keep is None else set(keep)
         got = {}
-        (self._prefill_lora if lora else self._prefill)(B, Lp, True, False)
+        self._start([text] * B, [prompt_text] * B, [prompt_speech] * B, B, Lp, True, False, lora=lora)
         if 0 in want:
             got[0] = st["logits"][:B, :self.cfg.out_vocab].clone()
         for i in range(1, len(forced) + 1):
-            (self._step_lora if lora else self._step)(B, True, False)
+            self._step(B, True, False, lora)
             if i in want:
                 got[i] = st["logits"][:B, :self.cfg.out_vocab].clone()
         order = list(range(len(forced) + 1)) if keep is None else list(keep)

@@ -72,8 +72,9 @@ class CosyVoice2Model:
         self.max_llm_requests = 4
         self.llm_lock = threading.Lock()          # only for LMs without decode contexts (the v1 TransformerLM)
         self._req_pool_lock = threading.Condition()
-        self._req_pool = None                     # [(context, stream)] free for requests
-        self._req_made = 0
+        self._req_pool = []                       # [(context, stream)] free for requests
+        self._req_made = 0                        # pairs made since the last reset (free or in use), <= max_llm_requests
+        self._req_gen = 0                         # counts the resets (_drop_contexts): a pair of an earlier one is stale
         self.flow_lock = threading.Lock()
         self.tts_speech_token_dict = {}
         self.llm_end_dict = {}
@@ -95,11 +96,13 @@ class CosyVoice2Model:
         would keep decoding with the old weights) and their captured graphs."""
         from . import ops
         with self._req_pool_lock:
-            ctxs = [c for c, _ in (self._req_pool or [])] + [c for c in (getattr(self, "_llm_contexts", None) or []) if c is not self.llm]
+            ctxs = [c for c, _ in self._req_pool] + [c for c in (getattr(self, "_llm_contexts", None) or []) if c is not self.llm]
             for c in ctxs:
                 ops.drop_graphs(getattr(c, "_graphs", {}))
-            self._req_pool, self._req_made = None, 0
+            # pairs that requests still hold belong to the generation that ends here: _release_llm discards them
+            self._req_pool, self._req_made, self._req_gen = [], 0, self._req_gen + 1
             self._llm_contexts = None
+            self._req_pool_lock.notify_all()      # requests waiting at the cap may make pairs of the new generation
 
     def load(self, llm_model, flow_model, hift_model):
         """model.py:71-81 — three flat state-dict files with the reference key names."""
@@ -121,21 +124,29 @@ class CosyVoice2Model:
         context is a Qwen2LM.new_context(): ``self.llm`` itself stays reserved for the batch paths (tts_batch / tts_batches use it
         without taking the pool), so a tts() request never shares KV caches or device state with a running batch."""
         with self._req_pool_lock:
-            if self._req_pool is None:
-                self._req_pool, self._req_made = [], 0
             while True:
                 if self._req_pool:
                     return self._req_pool.pop()
                 if self._req_made < self.max_llm_requests:
                     self._req_made += 1
+                    gen = self._req_gen
                     break
                 self._req_pool_lock.wait()
-        return self.llm.new_context(), torch.cuda.Stream(self.device, priority=-1)
+        ctx = self.llm.new_context()
+        ctx._pool_gen = gen
+        return ctx, torch.cuda.Stream(self.device, priority=-1)
 
     def _release_llm(self, pair):
+        """Back into the pool — unless the pair was taken before a reload (_drop_contexts): its context shares the OLD weight
+        tensors, so it is discarded with its captured graphs and counts for nothing in the pool that replaced its own."""
         with self._req_pool_lock:
-            self._req_pool.append(pair)
+            stale = pair[0]._pool_gen != self._req_gen
+            if not stale:
+                self._req_pool.append(pair)
             self._req_pool_lock.notify()
+        if stale:
+            from . import ops
+            ops.drop_graphs(getattr(pair[0], "_graphs", {}))
 
     def sync_lora(self, ctx):
         """A decode context made before ``self.llm.attach_lora(bank)`` (or before the bank was replaced) takes the LM's current bank."""
@@ -252,6 +263,8 @@ class CosyVoice2Model:
         try:
             if stream is True:
                 self.flow.length_bucket = self.stream_length_bucket
+                if getattr(self.flow, "supports_stream_cache", False):   # room for the encoder caches of all requests in flight
+                    self.flow.stream_cache_cap = max(self.flow.stream_cache_cap, self.max_llm_requests)
                 token_offset = 0
                 need = self.token_hop_len + self.flow.pre_lookahead_len
                 while True:
