@@ -1,9 +1,12 @@
-"""ctypes binding of libcosyvoice_amd.so (the C ABI declared in include/cosyvoice_amd.h).
+"""ctypes binding of libcosyvoice_amd.so (the C ABI declared in include/cosyvoice_amd.h, cosyvoice_amd_style.h and cosyvoice_amd_lora.h):
+the struct mirrors, one prototype per export, one loader.  Call sites pass plain ints, floats and ``data_ptr()`` values.
 
 The product path has NO fallback: if the library is missing or a call fails, this raises.
 """
 import ctypes as C
+import operator
 import os
+import threading
 
 import torch
 
@@ -239,52 +242,7 @@ class HiftDecodeDesc(C.Structure):
                 ("mel_cl", _vp), ("s", _vp), ("stft", _vp), ("a_pre", _vp), ("post", _vp), ("wav", _vp), ("lens", _vp)]
 
 
-_lib = None
-
-
-def lib():
-    """Load the HIP library or fail loudly (no CPU fallback exists in the product path)."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(
-                f"{LIB_PATH} not found: build it with `python -m cosyvoice_amd.build` (hipcc, gfx950). "
-                "cosyvoice_amd has no CPU fallback.")
-        _lib = C.CDLL(LIB_PATH)
-        _lib.cv_arch.restype = C.c_char_p
-        for name, st in (("gemm", GemmParams), ("norm", NormParams), ("attn", AttnParams), ("skinny", SkinnyParams),
-                         ("sample", SampleParams), ("groupnorm", GroupNormParams), ("tblock", TBlockParams), ("resblock", ResblockParams),
-                         ("spk_conv", SpkConvParams)):
-            fn = getattr(_lib, f"cv_sizeof_{name}_params")
-            if fn() != C.sizeof(st):
-                raise RuntimeError(f"ABI mismatch for cv_{name}_params: C {fn()} vs ctypes {C.sizeof(st)}")
-        for name, st in (("llm_step_desc", LlmStepDesc), ("llm_layer", LlmLayer), ("flow_solver_desc", FlowSolverDesc),
-                         ("flow_block", FlowBlock), ("flow_tblock", FlowTBlock), ("hift_decode_desc", HiftDecodeDesc),
-                         ("hift_stage", HiftStage), ("hift_resunit", HiftResunit)):
-            fn = getattr(_lib, f"cv_sizeof_{name}")
-            if fn() != C.sizeof(st):
-                raise RuntimeError(f"ABI mismatch for cv_{name}: C {fn()} vs ctypes {C.sizeof(st)}")
-    return _lib
-
-
-EXPORTS = ["cv_version", "cv_arch", "cv_gemm", "cv_layernorm", "cv_attention",
-           "cv_sizeof_gemm_params", "cv_sizeof_norm_params", "cv_sizeof_attn_params",
-           "cv_to_channels_last", "cv_to_channels_first", "cv_snake_multi", "cv_stft16", "cv_istft16", "cv_hift_source",
-           "cv_embedding", "cv_est_pack", "cv_cfm_update", "cv_graph_begin", "cv_graph_end", "cv_graph_launch",
-           "cv_graph_destroy", "cv_graph_launch_direct", "cv_graph_num_launches", "cv_stream_create_cumask",
-           "cv_stream_destroy", "cv_skinny_gemm", "cv_pack_skinny", "cv_rmsnorm_reduce", "cv_rope_append",
-           "cv_decode_attention", "cv_kv_retile", "cv_sample_ras", "cv_sizeof_skinny_params", "cv_sizeof_sample_params", "cv_anti_alias_act", "cv_anti_alias_act_cl",
-           "cv_stft_magnitude", "cv_log_clamp_channels_first", "cv_groupnorm_cl", "cv_groupnorm_workspace_floats",
-           "cv_interp_linear_cl", "cv_sizeof_groupnorm_params", "cv_relpos_append", "cv_sizeof_tblock_params", "cv_tblock_head",
-           "cv_tblock_tail", "cv_tblock_tail_head", "cv_sizeof_llm_step_desc", "cv_sizeof_llm_layer", "cv_llm_step_enqueue", "cv_llm_step_graph_create",
-           "cv_llm_step_graph_launch", "cv_llm_step_graph_destroy", "cv_sizeof_resblock_params", "cv_resblock_conv1", "cv_resblock_conv2",
-           "cv_sizeof_flow_solver_desc", "cv_sizeof_flow_block", "cv_sizeof_flow_tblock", "cv_flow_euler_enqueue",
-           "cv_flow_euler_graph_create", "cv_flow_euler_graph_launch", "cv_flow_euler_graph_destroy",
-           "cv_sizeof_hift_decode_desc", "cv_sizeof_hift_stage", "cv_sizeof_hift_resunit", "cv_hift_decode_enqueue", "cv_hift_decode",
-           "cv_hift_decode_graph_create", "cv_spk_power", "cv_spk_log_cmn", "cv_sizeof_spk_conv_params", "cv_spk_conv",
-           "cv_spk_cam_gate", "cv_spk_stats_pool"]
-
-# ---- speaker encoder v2 (include/cosyvoice_amd_style.h, csrc/style.hip): its own header, export list and size handshake
+# ---- speaker encoder v2 (include/cosyvoice_amd_style.h, csrc/style.hip)
 class WnLayerParams(C.Structure):
     _fields_ = [
         ("B", _i32), ("T", _i32), ("C", _i32), ("taps", _i32),
@@ -307,35 +265,7 @@ class GluConvParams(C.Structure):
     ]
 
 
-STYLE_EXPORTS = ["cv_sizeof_wn_layer_params", "cv_wn_layer", "cv_wn_gate", "cv_sizeof_glu_conv_params", "cv_glu_conv", "cv_gst_attention",
-                 "cv_style_attention", "cv_posterior_sample", "cv_masked_mean"]
-
-_style_lib = None
-
-
-def style_lib():
-    """The library with the style entry points bound: checks that it exports every STYLE_EXPORTS name and that the two parameter
-    blocks have the size the C side compiled (first use only)."""
-    global _style_lib
-    if _style_lib is None:
-        so = lib()
-        for name in STYLE_EXPORTS:
-            if not hasattr(so, name):
-                raise RuntimeError(f"{LIB_PATH} does not export {name}: rebuild it with `python -m cosyvoice_amd.build`")
-        for name, st in (("wn_layer", WnLayerParams), ("glu_conv", GluConvParams)):
-            fn = getattr(so, f"cv_sizeof_{name}_params")
-            if fn() != C.sizeof(st):
-                raise RuntimeError(f"ABI mismatch for cv_{name}_params: C {fn()} vs ctypes {C.sizeof(st)}")
-        so.cv_wn_gate.argtypes = [_vp, _i32, _vp, _i32, _i32, _i32, _vp]
-        so.cv_gst_attention.argtypes = [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp]
-        so.cv_style_attention.argtypes = [_vp, _vp, _vp, _i64, _i32, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _f32, _vp]
-        so.cv_posterior_sample.argtypes = [_vp, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp]
-        so.cv_masked_mean.argtypes = [_vp, _i64, _i32, _vp, _i32, _i32, _i32, _vp, _i32, _vp]
-        _style_lib = so
-    return _style_lib
-
-
-# ---- per-sequence LoRA (include/cosyvoice_amd_lora.h, csrc/lora.hip): its own header, export list and size handshake
+# ---- per-sequence LoRA (include/cosyvoice_amd_lora.h, csrc/lora.hip)
 LORA_ADD, LORA_STORE, LORA_SWIGLU = 0, 1, 2
 
 
@@ -363,26 +293,132 @@ class LoraExpandParams(C.Structure):
     ]
 
 
-LORA_EXPORTS = ["cv_sizeof_lora_shrink_params", "cv_lora_shrink", "cv_sizeof_lora_expand_params", "cv_lora_expand"]
+# ---- the binding: one prototype per export, one table of struct mirrors, one loader.  No call enters the library without a prototype.
+# header -> {export: one class letter per argument}: p pointer, i 32-bit integer or enum, q 64-bit integer, f float.  Every export returns
+# int (a cv_status, a size or a count) except those in RETURNS.  tests/test_abi_prototypes_cpu.py derives the same strings from the headers.
+PROTOTYPES = {
+    "cosyvoice_amd.h": {
+        "cv_version": "", "cv_arch": "", "cv_gemm": "pp", "cv_layernorm": "pp", "cv_attention": "pp",
+        "cv_sizeof_gemm_params": "", "cv_sizeof_norm_params": "", "cv_sizeof_attn_params": "",
+        "cv_to_channels_last": "ppiiiiip", "cv_to_channels_first": "ppiiiip", "cv_snake_multi": "piiiippiip",
+        "cv_stft16": "ppiiiip", "cv_istft16": "ppiiifp", "cv_hift_source": "pppppppiiiiffffp",
+        "cv_embedding": "pppiiiip", "cv_est_pack": "pppppiiiip", "cv_cfm_update": "ppiiiffp",
+        "cv_graph_begin": "p", "cv_graph_end": "pp", "cv_graph_launch": "pp", "cv_graph_destroy": "p",
+        "cv_graph_launch_direct": "pp", "cv_graph_num_launches": "p", "cv_stream_create_cumask": "pip", "cv_stream_destroy": "p",
+        "cv_skinny_gemm": "pp", "cv_pack_skinny": "ppiiip", "cv_rmsnorm_reduce": "pipiqipfpiiiip",
+        "cv_rope_append": "pipiiiippippiip", "cv_decode_attention": "pipppipiiiiifipipp", "cv_kv_retile": "ppppiiiip",
+        "cv_sample_ras": "pp", "cv_sizeof_skinny_params": "", "cv_sizeof_sample_params": "",
+        "cv_anti_alias_act": "ppiiiippppp", "cv_anti_alias_act_cl": "piipiiiiippppp",
+        "cv_stft_magnitude": "pipiiifp", "cv_log_clamp_channels_first": "pipiiifp",
+        "cv_groupnorm_cl": "pp", "cv_groupnorm_workspace_floats": "iii", "cv_interp_linear_cl": "piipiiiip",
+        "cv_sizeof_groupnorm_params": "", "cv_relpos_append": "ppppiiiip",
+        "cv_sizeof_tblock_params": "", "cv_tblock_head": "pp", "cv_tblock_tail": "pp", "cv_tblock_tail_head": "pp",
+        "cv_sizeof_llm_step_desc": "", "cv_sizeof_llm_layer": "", "cv_llm_step_enqueue": "pp", "cv_llm_step_graph_create": "ppp",
+        "cv_llm_step_graph_launch": "pp", "cv_llm_step_graph_destroy": "p",
+        "cv_sizeof_resblock_params": "", "cv_resblock_conv1": "pp", "cv_resblock_conv2": "pp",
+        "cv_sizeof_flow_solver_desc": "", "cv_sizeof_flow_block": "", "cv_sizeof_flow_tblock": "", "cv_flow_euler_enqueue": "pp",
+        "cv_flow_euler_graph_create": "ppp", "cv_flow_euler_graph_launch": "pp", "cv_flow_euler_graph_destroy": "p",
+        "cv_sizeof_hift_decode_desc": "", "cv_sizeof_hift_stage": "", "cv_sizeof_hift_resunit": "", "cv_hift_decode_enqueue": "pp",
+        "cv_hift_decode": "pp", "cv_hift_decode_graph_create": "ppp",
+        "cv_spk_power": "pipiiip", "cv_spk_log_cmn": "pipiiiipip", "cv_sizeof_spk_conv_params": "", "cv_spk_conv": "pp",
+        "cv_spk_cam_gate": "pqpiiipppppqp", "cv_spk_stats_pool": "pqipiiipppqp",
+    },
+    "cosyvoice_amd_style.h": {
+        "cv_sizeof_wn_layer_params": "", "cv_wn_layer": "pp", "cv_wn_gate": "pipiiip", "cv_sizeof_glu_conv_params": "", "cv_glu_conv": "pp",
+        "cv_gst_attention": "pipppiiiifp", "cv_style_attention": "pppqipqipiiifp", "cv_posterior_sample": "pippipiiip",
+        "cv_masked_mean": "pqipiiipip",
+    },
+    "cosyvoice_amd_lora.h": {
+        "cv_sizeof_lora_shrink_params": "", "cv_lora_shrink": "pp", "cv_sizeof_lora_expand_params": "", "cv_lora_expand": "pp",
+    },
+}
+RETURNS = {"cv_arch": "s", "cv_groupnorm_workspace_floats": "q"}     # s: const char*
+EXPORTS, STYLE_EXPORTS, LORA_EXPORTS = (list(v) for v in PROTOTYPES.values())
 
-_lora_lib = None
+# ctypes mirror, C struct, entry points whose first argument points to one (typed POINTER(mirror): another block raises in Python).
+# A struct is part of the size handshake when the library exports cv_sizeof_<its name without cv_>; the others are reached only through a
+# struct that is.  The prototype test compares every field's name, offset and size with the headers.
+STRUCTS = [
+    (GemmParams, "cv_gemm_params", ("cv_gemm",)),
+    (NormParams, "cv_norm_params", ("cv_layernorm",)),
+    (GroupNormParams, "cv_groupnorm_params", ("cv_groupnorm_cl",)),
+    (AttnParams, "cv_attn_params", ("cv_attention",)),
+    (SkinnyParams, "cv_skinny_params", ("cv_skinny_gemm",)),
+    (TBlockParams, "cv_tblock_params", ("cv_tblock_head", "cv_tblock_tail", "cv_tblock_tail_head")),
+    (ResblockParams, "cv_resblock_params", ("cv_resblock_conv1", "cv_resblock_conv2")),
+    (SampleParams, "cv_sample_params", ("cv_sample_ras",)),
+    (SpkConvParams, "cv_spk_conv_params", ("cv_spk_conv",)),
+    (LlmLayer, "cv_llm_layer", ()),
+    (LlmStepDesc, "cv_llm_step_desc", ("cv_llm_step_enqueue", "cv_llm_step_graph_create")),
+    (FlowResnet, "cv_flow_resnet", ()),
+    (FlowTBlock, "cv_flow_tblock", ()),
+    (FlowBlock, "cv_flow_block", ()),
+    (FlowSolverDesc, "cv_flow_solver_desc", ("cv_flow_euler_enqueue", "cv_flow_euler_graph_create")),
+    (HiftConv, "cv_hift_conv", ()),
+    (HiftResunit, "cv_hift_resunit", ()),
+    (HiftResblock, "cv_hift_resblock", ()),
+    (HiftPhase, "cv_hift_phase", ()),
+    (HiftStage, "cv_hift_stage", ()),
+    (HiftDecodeDesc, "cv_hift_decode_desc", ("cv_hift_decode_enqueue", "cv_hift_decode", "cv_hift_decode_graph_create")),
+    (WnLayerParams, "cv_wn_layer_params", ("cv_wn_layer",)),
+    (GluConvParams, "cv_glu_conv_params", ("cv_glu_conv",)),
+    (LoraSegment, "cv_lora_segment", ()),
+    (LoraShrinkParams, "cv_lora_shrink_params", ("cv_lora_shrink",)),
+    (LoraExpandParams, "cv_lora_expand_params", ("cv_lora_expand",)),
+]
 
 
-def lora_lib():
-    """The library with the LoRA entry points bound: checks that it exports every LORA_EXPORTS name and that the two parameter blocks
-    have the size the C side compiled (first use only)."""
-    global _lora_lib
-    if _lora_lib is None:
-        so = lib()
-        for name in LORA_EXPORTS:
-            if not hasattr(so, name):
-                raise RuntimeError(f"{LIB_PATH} does not export {name}: rebuild it with `python -m cosyvoice_amd.build`")
-        for name, st in (("lora_shrink", LoraShrinkParams), ("lora_expand", LoraExpandParams)):
-            fn = getattr(so, f"cv_sizeof_{name}_params")
-            if fn() != C.sizeof(st):
-                raise RuntimeError(f"ABI mismatch for cv_{name}_params: C {fn()} vs ctypes {C.sizeof(st)}")
-        _lora_lib = so
-    return _lora_lib
+
+class _Int32Arg:
+    """argtypes entry of a 32-bit integer argument: hands ctypes the Python int itself, which it passes as a C int; operator.index refuses
+    floats and None.  c_int32.from_param builds an argument object for every one of them, and two arguments in three are such ints: a
+    call then costs half as much again (profiles/abi_prototypes_host.json)."""
+    from_param = operator.index
+
+
+_ARG = {"p": _vp, "i": _Int32Arg, "q": _i64, "f": _f32}
+_RET = {"i": _i32, "q": _i64, "s": C.c_char_p}
+_lib = None
+_lock = threading.Lock()
+
+
+def _load():
+    if not os.path.exists(LIB_PATH):
+        raise RuntimeError(
+            f"{LIB_PATH} not found: build it with `python -m cosyvoice_amd.build` (hipcc, gfx950). "
+            "cosyvoice_amd has no CPU fallback.")
+    so = C.CDLL(LIB_PATH)
+    protos = {name: sig for table in PROTOTYPES.values() for name, sig in table.items()}
+    for name in protos:
+        if not hasattr(so, name):
+            raise RuntimeError(f"{LIB_PATH} does not export {name}: rebuild it with `python -m cosyvoice_amd.build`")
+    args = {name: [_ARG[c] for c in sig] for name, sig in protos.items()}
+    for st, _, entries in STRUCTS:
+        for name in entries:
+            assert protos[name][0] == "p", name
+            args[name][0] = C.POINTER(st)
+    for name, a in args.items():
+        fn = getattr(so, name)
+        fn.restype, fn.argtypes = _RET[RETURNS.get(name, "i")], a
+    for st, cname, _ in STRUCTS:
+        probe = "cv_sizeof_" + cname[3:]
+        if probe in protos and getattr(so, probe)() != C.sizeof(st):
+            raise RuntimeError(f"ABI mismatch for {cname}: C {getattr(so, probe)()} vs ctypes {C.sizeof(st)}")
+    return so
+
+
+def lib():
+    """Load the HIP library or fail loudly (no CPU fallback exists in the product path).  The handle is published only once every export
+    of the three headers is present and has its prototype and the size handshake has passed, and under a lock: no thread sees it earlier."""
+    global _lib
+    if _lib is None:
+        with _lock:
+            if _lib is None:
+                _lib = _load()
+    return _lib
+
+
+style_lib = lora_lib = lib      # one loader binds all three headers; the names stay for their callers
 
 
 TORCH_DT = {torch.float32: CV_F32, torch.bfloat16: CV_BF16, torch.float16: CV_F16}

@@ -2,7 +2,6 @@
 (/root/reference/cosyvoice/BigVGAN/alias_free_activation/cuda/activation1d.py:36-76), whose CUDA extension
 (anti_alias_activation_cuda.cu) is the reference's only native kernel.  Same call contract: ``forward(x [B,C,T])`` with
 a Snake / SnakeBeta activation object carrying ``alpha`` (and ``beta``) and ``alpha_logscale``."""
-import ctypes as C
 import math
 
 import torch
@@ -46,9 +45,8 @@ class Activation1d:
         B, Cc, T = x.shape
         y = torch.empty_like(x)
         a, b = self._log_params()
-        L.check(L.lib().cv_anti_alias_act(C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), L.TORCH_DT[x.dtype], B, Cc, T,
-                                          C.c_void_p(self.up_filter.data_ptr()), C.c_void_p(self.down_filter.data_ptr()),
-                                          C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), L.stream_ptr()), "cv_anti_alias_act")
+        L.check(L.lib().cv_anti_alias_act(x.data_ptr(), y.data_ptr(), L.TORCH_DT[x.dtype], B, Cc, T, self.up_filter.data_ptr(),
+                                          self.down_filter.data_ptr(), a.data_ptr(), b.data_ptr(), L.stream_ptr()), "cv_anti_alias_act")
         return y
 
     __call__ = forward
@@ -66,10 +64,9 @@ from .weights import fold_weight_norm  # noqa: E402
 def anti_alias_act_cl(x, y, C_, up_filter, down_filter, alpha_log, beta_log):
     """x (B,T,ldx) -> y (B,T,ldy), first ``C_`` channels: UpSample1d(2) -> SnakeBeta -> DownSample1d(2), channels-last."""
     B, T, _ = x.shape
-    L.check(L.lib().cv_anti_alias_act_cl(C.c_void_p(x.data_ptr()), x.stride(1), L.TORCH_DT[x.dtype], C.c_void_p(y.data_ptr()),
-                                         y.stride(1), L.TORCH_DT[y.dtype], B, T, C_, C.c_void_p(up_filter.data_ptr()),
-                                         C.c_void_p(down_filter.data_ptr()), C.c_void_p(alpha_log.data_ptr()),
-                                         C.c_void_p(beta_log.data_ptr()), L.stream_ptr()), "cv_anti_alias_act_cl")
+    L.check(L.lib().cv_anti_alias_act_cl(x.data_ptr(), x.stride(1), L.TORCH_DT[x.dtype], y.data_ptr(), y.stride(1), L.TORCH_DT[y.dtype],
+                                         B, T, C_, up_filter.data_ptr(), down_filter.data_ptr(), alpha_log.data_ptr(),
+                                         beta_log.data_ptr(), L.stream_ptr()), "cv_anti_alias_act_cl")
 
 
 class BigVGAN:

@@ -18,7 +18,6 @@ strided view of the signal; torchaudio is not a pinned part of the reference, so
 restated — **parity unpinned at that boundary**), ``MelSpectrogram.ragged`` (prompts of different lengths in one
 pass, every row bit-identical to that prompt alone) and ``PromptFrontEnd`` (the ``model_input`` dicts of cli/frontend.py:141-195
 and the argument lists of ``CosyVoice2Model.tts_batch``)."""
-import ctypes as C
 import math
 
 import numpy as np
@@ -114,13 +113,13 @@ class MelSpectrogram:
         ops.gemm(buf, self.dft, T, self.ld_spec, self.n_fft, batch=B, a_bs=(ldp, 0), lda=self.hop, a_rows=T,
                  out_f32=spec, o32_bs=(spec.stride(0), 0), ldo32=self.ld_spec)
         mag = torch.empty(B * T, self.ld_mag, device=self.device)
-        L.check(L.lib().cv_stft_magnitude(C.c_void_p(spec.data_ptr()), self.ld_spec, C.c_void_p(mag.data_ptr()), self.ld_mag, B * T,
-                                          self.nbins, C.c_float(1e-9), L.stream_ptr()), "cv_stft_magnitude")
+        L.check(L.lib().cv_stft_magnitude(spec.data_ptr(), self.ld_spec, mag.data_ptr(), self.ld_mag, B * T, self.nbins, 1e-9,
+                                          L.stream_ptr()), "cv_stft_magnitude")
         melo = torch.empty(B * T, self.n_mels, device=self.device)
         ops.gemm(mag, self.mel, B * T, self.n_mels, self.ld_mag, lda=self.ld_mag, out_f32=melo, ldo32=self.n_mels)
         out = torch.empty(B, self.n_mels, T, device=self.device)
-        L.check(L.lib().cv_log_clamp_channels_first(C.c_void_p(melo.data_ptr()), self.n_mels, C.c_void_p(out.data_ptr()), B, T,
-                                                    self.n_mels, C.c_float(1e-5), L.stream_ptr()), "cv_log_clamp_channels_first")
+        L.check(L.lib().cv_log_clamp_channels_first(melo.data_ptr(), self.n_mels, out.data_ptr(), B, T, self.n_mels, 1e-5,
+                                                    L.stream_ptr()), "cv_log_clamp_channels_first")
         return out
 
     def num_frames(self, S: int) -> int:

@@ -13,7 +13,6 @@ with the few t-dependent fields patched: 1.03 ms per token at full size (14 laye
 full-recompute path it is checked against (``incremental = False``: the whole causal pass per step, the cached step being its
 last row; both match the reference's own cached loop, oracle/llm_v1.py 3e-6).  Sampling is ``cv_sample_ras`` in its
 non-random-RAS mode."""
-import ctypes as C
 import math
 from types import SimpleNamespace
 from typing import Generator, List, Optional
@@ -108,7 +107,6 @@ class _CausalStack(UpsampleConformerEncoder):
         patches = []          # (params struct, field, base address, bytes per step of t)
         self._len_fields, self._t_args = [], []
         cdt = L.TORCH_DT[dt]
-        vp = lambda t_: C.c_void_p(t_.data_ptr())
         rec = ops.Recorder()
         with rec:
             # LegacyLinearNoSubsampling on row t: Linear -> LayerNorm -> ReLU, x sqrt(D)
@@ -119,7 +117,7 @@ class _CausalStack(UpsampleConformerEncoder):
                 w = self.dw[i]
                 ops.layernorm(b["xs"], l["g_mha"], l["b_mha"], 1e-12, out_act=b["xn"][:1])
                 ops.skinny_gemm(b["xn"], w["qkv"], 1, 4 * D, D, bias=w["bqkv"], out_f32=b["qkv"], ldo=4 * D)
-                args = [vp(b["qkv"]), vp(b["qq"]), vp(self.kc[i]), vp(self.vtc[i]), cdt, D, 0, Tpm]
+                args = [b["qkv"].data_ptr(), b["qq"].data_ptr(), self.kc[i].data_ptr(), self.vtc[i].data_ptr(), cdt, D, 0, Tpm]
                 rec.add_raw("cv_relpos_append", args)
                 self._t_args.append(args)
                 ops.gemm(b["qq"][:, D:], self.prev[i], 1, 1, 64, batch=H, a_bs=(64, 0), lda=2 * D, w_bs=(64, 0), ldw=D,

@@ -235,7 +235,7 @@ def to_channels_last(x, out):
     """x (B,C,T) fp32 -> out (B,T,ld) any dtype, zero-filled pad columns."""
     _req_cuda(x, out)
     B, Cc, T = x.shape
-    L.check(L.lib().cv_to_channels_last(C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()), L.TORCH_DT[out.dtype], B, Cc, T,
+    L.check(L.lib().cv_to_channels_last(x.data_ptr(), out.data_ptr(), L.TORCH_DT[out.dtype], B, Cc, T,
                                         out.stride(1), L.stream_ptr()), "cv_to_channels_last")
 
 
@@ -244,7 +244,7 @@ def to_channels_first(x, out, Cc=None):
     _req_cuda(x, out)
     B, T, _ = x.shape
     Cc = out.shape[1] if Cc is None else Cc
-    L.check(L.lib().cv_to_channels_first(C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()), B, Cc, T, x.stride(1),
+    L.check(L.lib().cv_to_channels_first(x.data_ptr(), out.data_ptr(), B, Cc, T, x.stride(1),
                                          L.stream_ptr()), "cv_to_channels_first")
 
 
@@ -255,61 +255,56 @@ def snake_multi(x2d, alphas, outs, split=False):
     n = len(alphas)
     a = (C.c_void_p * n)(*[t.data_ptr() for t in alphas])
     o = (C.c_void_p * n)(*[t.data_ptr() for t in outs])
-    L.check(L.lib().cv_snake_multi(C.c_void_p(x2d.data_ptr()), x2d.shape[0], x2d.shape[1], x2d.stride(0), n, a, o,
+    L.check(L.lib().cv_snake_multi(x2d.data_ptr(), x2d.shape[0], x2d.shape[1], x2d.stride(0), n, a, o,
                                    outs[0].stride(0), L.CV_F32X3 if split else L.TORCH_DT[outs[0].dtype], L.stream_ptr()), "cv_snake_multi")
 
 
 def stft16(s, out):
     """s (B,S) fp32 -> out (B, S/4+1, ld>=18)."""
     _req_cuda(s, out)
-    L.check(L.lib().cv_stft16(C.c_void_p(s.data_ptr()), C.c_void_p(out.data_ptr()), L.TORCH_DT[out.dtype], s.shape[0], s.shape[1],
+    L.check(L.lib().cv_stft16(s.data_ptr(), out.data_ptr(), L.TORCH_DT[out.dtype], s.shape[0], s.shape[1],
                               out.stride(1), L.stream_ptr()), "cv_stft16")
 
 
 def istft16(y, wav, audio_limit):
     """y (B,F,ld>=18) fp32 -> wav (B,(F-1)*4) fp32."""
     _req_cuda(y, wav)
-    L.check(L.lib().cv_istft16(C.c_void_p(y.data_ptr()), C.c_void_p(wav.data_ptr()), y.shape[0], y.shape[1], y.stride(1),
-                               C.c_float(audio_limit), L.stream_ptr()), "cv_istft16")
+    L.check(L.lib().cv_istft16(y.data_ptr(), wav.data_ptr(), y.shape[0], y.shape[1], y.stride(1), audio_limit, L.stream_ptr()),
+            "cv_istft16")
 
 
 def hift_source(f0, phase_vec, noise, lin_w, lin_b, work, s, up, sampling_rate, sine_amp, noise_std, vthr):
     _req_cuda(f0, phase_vec, noise, lin_w, lin_b, work, s)
     B, T = f0.shape
     nh = phase_vec.shape[1]
-    L.check(L.lib().cv_hift_source(C.c_void_p(f0.data_ptr()), C.c_void_p(phase_vec.data_ptr()), C.c_void_p(noise.data_ptr()),
-                                   C.c_void_p(lin_w.data_ptr()), C.c_void_p(lin_b.data_ptr()), C.c_void_p(work.data_ptr()),
-                                   C.c_void_p(s.data_ptr()), B, T, up, nh, C.c_float(sampling_rate), C.c_float(sine_amp),
-                                   C.c_float(noise_std), C.c_float(vthr), L.stream_ptr()), "cv_hift_source")
+    L.check(L.lib().cv_hift_source(f0.data_ptr(), phase_vec.data_ptr(), noise.data_ptr(), lin_w.data_ptr(), lin_b.data_ptr(),
+                                   work.data_ptr(), s.data_ptr(), B, T, up, nh, sampling_rate, sine_amp, noise_std, vthr,
+                                   L.stream_ptr()), "cv_hift_source")
 
 
 # ----------------------------------------------------------------------------- flow helpers / graphs
 def embedding(table, idx, out):
     """table (V,dim) fp32, idx (rows,) int32, out (rows, ld) any dtype."""
     _req_cuda(table, idx, out)
-    L.check(L.lib().cv_embedding(C.c_void_p(table.data_ptr()), C.c_void_p(idx.data_ptr()), C.c_void_p(out.data_ptr()),
-                                 L.TORCH_DT[out.dtype], idx.numel(), table.shape[1], out.stride(-2), L.stream_ptr()), "cv_embedding")
+    L.check(L.lib().cv_embedding(table.data_ptr(), idx.data_ptr(), out.data_ptr(), L.TORCH_DT[out.dtype], idx.numel(), table.shape[1],
+                                 out.stride(-2), L.stream_ptr()), "cv_embedding")
 
 
 def est_pack(x, mu, spks, cond, xin):
     _req_cuda(x, mu, spks, cond, xin)
     B, T, Cc = x.shape
-    L.check(L.lib().cv_est_pack(C.c_void_p(x.data_ptr()), C.c_void_p(mu.data_ptr()), C.c_void_p(spks.data_ptr()),
-                                C.c_void_p(cond.data_ptr()), C.c_void_p(xin.data_ptr()), L.TORCH_DT[xin.dtype], B, T, Cc,
-                                L.stream_ptr()), "cv_est_pack")
+    L.check(L.lib().cv_est_pack(x.data_ptr(), mu.data_ptr(), spks.data_ptr(), cond.data_ptr(), xin.data_ptr(), L.TORCH_DT[xin.dtype],
+                                B, T, Cc, L.stream_ptr()), "cv_est_pack")
 
 
 def cfm_update(x, v, dt, cfg_rate):
     _req_cuda(x, v)
     B, T, Cc = x.shape
-    L.check(L.lib().cv_cfm_update(C.c_void_p(x.data_ptr()), C.c_void_p(v.data_ptr()), B, T, Cc, C.c_float(dt), C.c_float(cfg_rate),
-                                  L.stream_ptr()), "cv_cfm_update")
+    L.check(L.lib().cv_cfm_update(x.data_ptr(), v.data_ptr(), B, T, Cc, dt, cfg_rate, L.stream_ptr()), "cv_cfm_update")
 
 
 def groupnorm_workspace(B, T, groups, device):
-    f = L.lib().cv_groupnorm_workspace_floats
-    f.restype = C.c_int64
-    return torch.empty(int(f(B, T, groups)), device=device, dtype=torch.float32)
+    return torch.empty(L.lib().cv_groupnorm_workspace_floats(B, T, groups), device=device, dtype=torch.float32)
 
 
 def groupnorm_cl(x, groups, gamma, beta, eps, partial, *, act=ACT_NONE, add=None, out_f32=None, out_act=None):
@@ -336,7 +331,7 @@ def interp_linear_cl(x, y):
     """x (T_in, C) fp32 rows (stride(0) = ld) -> y (T_out, C) any dtype: F.interpolate(mode='linear') along T."""
     _req_cuda(x, y)
     assert x.dtype == torch.float32 and x.shape[1] == y.shape[1] and x.stride(1) == 1 and y.stride(1) == 1
-    L.check(L.lib().cv_interp_linear_cl(C.c_void_p(x.data_ptr()), x.stride(0), x.shape[0], C.c_void_p(y.data_ptr()), y.stride(0),
+    L.check(L.lib().cv_interp_linear_cl(x.data_ptr(), x.stride(0), x.shape[0], y.data_ptr(), y.stride(0),
                                         L.TORCH_DT[y.dtype], y.shape[0], x.shape[1], L.stream_ptr()), "cv_interp_linear_cl")
 
 
@@ -429,7 +424,7 @@ def destroy_masked_stream(stream):
     h = stream.cuda_stream
     if _MASKED_STREAMS.pop(h, None) is not None:
         stream.synchronize()
-        L.check(L.lib().cv_stream_destroy(C.c_void_p(h)), "cv_stream_destroy")
+        L.check(L.lib().cv_stream_destroy(h), "cv_stream_destroy")
 
 
 def close():
@@ -450,7 +445,7 @@ def close():
             pass
     for h, st in list(_MASKED_STREAMS.items()):
         try:
-            L.lib().cv_stream_destroy(C.c_void_p(h))
+            L.lib().cv_stream_destroy(h)
         except Exception:
             pass
     _MASKED_STREAMS.clear()
@@ -486,7 +481,7 @@ def pack_skinny(W, interleave=False):
     N, K = W.shape
     ntiles = (N + 15) // 16
     Wp = torch.empty(ntiles * (K // 32) * 64 * 8, device=W.device, dtype=W.dtype)
-    L.check(L.lib().cv_pack_skinny(C.c_void_p(W.data_ptr()), C.c_void_p(Wp.data_ptr()), N, K, int(interleave), L.stream_ptr()),
+    L.check(L.lib().cv_pack_skinny(W.data_ptr(), Wp.data_ptr(), N, K, int(interleave), L.stream_ptr()),
             "cv_pack_skinny")
     return Wp
 
@@ -522,24 +517,22 @@ def skinny_gemm(A, Wp, M, N, K, *, bias=None, ksplit=1, mode=0, out_f32=None, ld
 
 def rmsnorm_reduce(x, gamma, eps, xn, rows, *, slabs=None, nslab=0, slab_stride=0, ld_slab=0):
     _req_cuda(x, gamma, xn, slabs)
-    L.check(L.lib().cv_rmsnorm_reduce(C.c_void_p(x.data_ptr()), x.stride(0), C.c_void_p(L.ptr(slabs)), nslab, C.c_int64(slab_stride), ld_slab,
-                                      C.c_void_p(gamma.data_ptr()), C.c_float(eps), C.c_void_p(xn.data_ptr()), xn.stride(0),
-                                      L.TORCH_DT[xn.dtype], rows, x.shape[1], L.stream_ptr()), "cv_rmsnorm_reduce")
+    L.check(L.lib().cv_rmsnorm_reduce(x.data_ptr(), x.stride(0), L.ptr(slabs), nslab, slab_stride, ld_slab, gamma.data_ptr(), eps,
+                                      xn.data_ptr(), xn.stride(0), L.TORCH_DT[xn.dtype], rows, x.shape[1], L.stream_ptr()), "cv_rmsnorm_reduce")
 
 
 def rope_append(qkv, pos_base, rows, rows_per_seq, Hq, Hkv, inv_freq, q_out, kcache, vtcache, ctx_max):
     _req_cuda(qkv, pos_base, inv_freq, q_out, kcache, vtcache)
-    L.check(L.lib().cv_rope_append(C.c_void_p(qkv.data_ptr()), qkv.stride(0), C.c_void_p(pos_base.data_ptr()), rows, rows_per_seq,
-                                   Hq, Hkv, C.c_void_p(inv_freq.data_ptr()), C.c_void_p(q_out.data_ptr()), q_out.stride(0),
-                                   C.c_void_p(kcache.data_ptr()), C.c_void_p(vtcache.data_ptr()), ctx_max, L.TORCH_DT[q_out.dtype],
-                                   L.stream_ptr()), "cv_rope_append")
+    L.check(L.lib().cv_rope_append(qkv.data_ptr(), qkv.stride(0), pos_base.data_ptr(), rows, rows_per_seq, Hq, Hkv, inv_freq.data_ptr(),
+                                   q_out.data_ptr(), q_out.stride(0), kcache.data_ptr(), vtcache.data_ptr(), ctx_max,
+                                   L.TORCH_DT[q_out.dtype], L.stream_ptr()), "cv_rope_append")
 
 
 def kv_retile(k_rm, vt_rm, k_tiled, vt_tiled, B, Hkv, ctx_max, n_keys):
     """Row-major caches (rope_append's layout) -> the fragment-tiled caches the fused decode_attention reads and appends to."""
     _req_cuda(k_rm, vt_rm, k_tiled, vt_tiled)
-    L.check(L.lib().cv_kv_retile(C.c_void_p(k_rm.data_ptr()), C.c_void_p(vt_rm.data_ptr()), C.c_void_p(k_tiled.data_ptr()),
-                                 C.c_void_p(vt_tiled.data_ptr()), B, Hkv, ctx_max, n_keys, L.stream_ptr()), "cv_kv_retile")
+    L.check(L.lib().cv_kv_retile(k_rm.data_ptr(), vt_rm.data_ptr(), k_tiled.data_ptr(), vt_tiled.data_ptr(), B, Hkv, ctx_max, n_keys,
+                                 L.stream_ptr()), "cv_kv_retile")
 
 
 def kv_tile_index(ctx_max, key, d, v=False):
@@ -556,11 +549,9 @@ def kv_tile_index(ctx_max, key, d, v=False):
 def decode_attention(q, kcache, vtcache, ctx_len, ctx_add, out, B, Hq, Hkv, ctx_max, scale, qkv=None, inv_freq=None):
     """qkv (fp32 [B][ld]) + inv_freq: fused RoPE + KV append + attention (q then only carries the dtype)."""
     _req_cuda(q, kcache, vtcache, ctx_len, out, qkv, inv_freq)
-    L.check(L.lib().cv_decode_attention(C.c_void_p(q.data_ptr()), q.stride(0), C.c_void_p(kcache.data_ptr()),
-                                        C.c_void_p(vtcache.data_ptr()), C.c_void_p(ctx_len.data_ptr()), ctx_add,
-                                        C.c_void_p(out.data_ptr()), out.stride(0), B, Hq, Hkv, ctx_max, C.c_float(scale),
-                                        L.TORCH_DT[q.dtype], C.c_void_p(L.ptr(qkv)), (qkv.stride(0) if qkv is not None else 0),
-                                        C.c_void_p(L.ptr(inv_freq)), L.stream_ptr()), "cv_decode_attention")
+    L.check(L.lib().cv_decode_attention(q.data_ptr(), q.stride(0), kcache.data_ptr(), vtcache.data_ptr(), ctx_len.data_ptr(), ctx_add,
+                                        out.data_ptr(), out.stride(0), B, Hq, Hkv, ctx_max, scale, L.TORCH_DT[q.dtype], L.ptr(qkv),
+                                        (qkv.stride(0) if qkv is not None else 0), L.ptr(inv_freq), L.stream_ptr()), "cv_decode_attention")
 
 
 def sample_ras(params):

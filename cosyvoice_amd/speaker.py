@@ -91,11 +91,11 @@ class _Fbank:
         ops.gemm(wave, self.dft, T, 2 * NBINS, WIN, batch=B, a_bs=(ldw, 0), lda=HOP, a_rows=T, out_f32=spec,
                  o32_bs=(T * 2 * NBINS, 0), ldo32=2 * NBINS, dtype=L.CV_F32)
         st = L.stream_ptr()
-        _check(L.lib().cv_spk_power(C.c_void_p(spec.data_ptr()), 2 * NBINS, C.c_void_p(pw.data_ptr()), NBINS, B * T, NBINS, st),
+        _check(L.lib().cv_spk_power(spec.data_ptr(), 2 * NBINS, pw.data_ptr(), NBINS, B * T, NBINS, st),
                "cv_spk_power")
         ops.gemm(pw, self.mel, B * T, NMELS, NBINS, lda=NBINS, out_f32=melo, ldo32=NMELS, dtype=L.CV_F32)
-        _check(L.lib().cv_spk_log_cmn(C.c_void_p(melo.data_ptr()), NMELS, C.c_void_p(lens.data_ptr()), B, T, NMELS, int(cmn),
-                                      C.c_void_p(out.data_ptr()), ldo, st), "cv_spk_log_cmn")
+        _check(L.lib().cv_spk_log_cmn(melo.data_ptr(), NMELS, lens.data_ptr(), B, T, NMELS, int(cmn),
+                                      out.data_ptr(), ldo, st), "cv_spk_log_cmn")
 
 
 def _pad_waves(waves):
@@ -312,10 +312,9 @@ class CAMPPlus:
                 cin = ch + 32 * i
                 cv(X, T2 * Cb, Cb, T2, 1, cin, q["w1"], h, T2 * 128, 128, T2, 1, B, pre=q["pre"], bias=q["b1"], relu=True,
                    in_len=lens2, out_len=lens2, psum=psum, psum_bs=psum_bs)
-                _check(L.lib().cv_spk_cam_gate(C.c_void_p(psum.data_ptr()), C.c_int64(psum_bs), C.c_void_p(lens2.data_ptr()), B, T2,
-                                               SEG_LEN, C.c_void_p(q["g1"].data_ptr()), C.c_void_p(q["gb1"].data_ptr()),
-                                               C.c_void_p(q["g2"].data_ptr()), C.c_void_p(q["gb2"].data_ptr()),
-                                               C.c_void_p(gate.data_ptr()), C.c_int64(gate_bs), st), "cv_spk_cam_gate")
+                _check(L.lib().cv_spk_cam_gate(psum.data_ptr(), psum_bs, lens2.data_ptr(), B, T2, SEG_LEN, q["g1"].data_ptr(),
+                                               q["gb1"].data_ptr(), q["g2"].data_ptr(), q["gb2"].data_ptr(), gate.data_ptr(), gate_bs, st),
+                       "cv_spk_cam_gate")
                 cv(h, T2 * 128, 128, T2, 1, 128, q["wl"], X, T2 * Cb, Cb, T2, 1, B, k=(1, 3), pad=(0, dil), dt=dil, in_len=lens2,
                    out_len=lens2, gate=gate, gate_bs=gate_bs, y_off=cin)
             ch += 32 * n
@@ -324,9 +323,8 @@ class CAMPPlus:
             cv(X, T2 * Cb, Cb, T2, 1, Cb, t["w"], Y, T2 * Cy, Cy, T2, 1, B, pre=t["pre"], in_len=lens2, out_len=lens2)
             ch //= 2
         sc, sh = P["out_nl"]
-        _check(L.lib().cv_spk_stats_pool(C.c_void_p(ws["tr3"].data_ptr()), C.c_int64(T2 * 512), 512, C.c_void_p(lens2.data_ptr()), B, T2,
-                                         512, C.c_void_p(sc.data_ptr()), C.c_void_p(sh.data_ptr()), C.c_void_p(ws["stats"].data_ptr()),
-                                         C.c_int64(1024), st), "cv_spk_stats_pool")
+        _check(L.lib().cv_spk_stats_pool(ws["tr3"].data_ptr(), T2 * 512, 512, lens2.data_ptr(), B, T2, 512, sc.data_ptr(), sh.data_ptr(),
+                                         ws["stats"].data_ptr(), 1024, st), "cv_spk_stats_pool")
         cv(ws["stats"], 1024, 1024, 1, 1, 1024, P["dense"][0], ws["emb"], CAMPPLUS_EMBED, CAMPPLUS_EMBED, 1, 1, B, bias=P["dense"][1])
 
     def _run(self, key, B, T, frames, fill, S_pad=0, graph=True):

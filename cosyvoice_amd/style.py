@@ -50,10 +50,6 @@ def num_frames(S: int) -> int:
     return int(S) // HOP
 
 
-def _vp(t):
-    return C.c_void_p(t.data_ptr())
-
-
 def _stage_reflect(buf, S, ld):
     """buf (B, S_max) with S[b] valid samples per row -> (B, ld): row b = its own samples reflect-padded by 362 at both of ITS ends,
     zeros behind.  What ``buf`` holds past a row's length is never read."""
@@ -81,7 +77,7 @@ def _enqueue_spectrogram(dft, stage, ld_stage, B, T, spec, mag):
     """stage (B, ld_stage) -> mag (B * T, LD_MAG): frame t of row b = stage[b, 300 t : 300 t + 1024] (lda = hop)."""
     ops.gemm(stage, dft, T, LD_SPEC, NFFT, batch=B, a_bs=(ld_stage, 0), lda=HOP, a_rows=T, out_f32=spec, o32_bs=(T * LD_SPEC, 0),
              ldo32=LD_SPEC, dtype=L.CV_F32)
-    L.check(L.lib().cv_stft_magnitude(_vp(spec), LD_SPEC, _vp(mag), LD_MAG, B * T, NBINS, C.c_float(1e-6), L.stream_ptr()),
+    L.check(L.lib().cv_stft_magnitude(spec.data_ptr(), LD_SPEC, mag.data_ptr(), LD_MAG, B * T, NBINS, 1e-6, L.stream_ptr()),
             "cv_stft_magnitude")
 
 
