@@ -10,6 +10,7 @@
 // K / V^T tiles (64 keys) are staged through LDS, double-buffered with register prefetch (one barrier per tile).
 #include <type_traits>
 #include "cv_device.h"
+#include "attn_select.h"
 
 namespace {
 
@@ -17,9 +18,7 @@ constexpr int KT_BYTES = 8192;        // K tile: 64 keys x 128 B, row-major with
 constexpr int VT_PITCH = 128;         // bytes per d-row of the V^T tile; 16-byte chunk slots XOR-swizzled by (row >> 1) & 7
 constexpr int VT_BYTES = 64 * VT_PITCH;
 constexpr int STAGE_BYTES = KT_BYTES + VT_BYTES;
-constexpr float NEG_BIG = -1e30f;
-
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+static_assert(STAGE_BYTES == ATTN_STAGE_BYTES, "attn_select sizes the LDS");
 
 // max over the four lanes that hold one query's scores (lane, lane^16, lane^32, lane^48): two v_permlane*_swap + v_max
 // instead of two ds_bpermute round trips through the LDS crossbar.
@@ -358,7 +357,7 @@ __device__ __forceinline__ f32x16_t mfma32(const uint4& a, const uint4& b, f32x1
   else return __builtin_amdgcn_mfma_f32_32x32x16_f16(bitcast<f16x8_t>(a), bitcast<f16x8_t>(b), c, 0, 0, 0);
 }
 
-template <int DT, int NWV, int ABL = 0>   // ABL: timing-only ablations (wrong results; instantiated by hand for a measurement, DESIGN.md §6 Round 3, "Timing ablations of form (i)"): 1 no K/V tile traffic after tile 0, 2 no softmax arithmetic
+template <int DT, int NWV>
 __global__ __launch_bounds__(64 * NWV, NWV == 4 ? 3 : 2) void attn32_kernel(const cv_attn_params p) {
   constexpr int NT = 64 * NWV, QW = 32 * NWV, NL = 512 / NT;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -466,8 +465,8 @@ __global__ __launch_bounds__(64 * NWV, NWV == 4 ? 3 : 2) void attn32_kernel(cons
 
   auto tile = [&](auto masked_tag, const int t) {
     constexpr bool MASKED = decltype(masked_tag)::value;
-    const int s = (ABL & 1) ? 0 : (t & 1);
-    if (!(ABL & 1) && t + 1 < ntiles) load_tile(t + 1);
+    const int s = t & 1;
+    if (t + 1 < ntiles) load_tile(t + 1);
     const char* sk = smem + s * STAGE_BYTES;
     const char* sv = sk + KT_BYTES;
     const int j0 = t << 6;
@@ -548,7 +547,6 @@ __global__ __launch_bounds__(64 * NWV, NWV == 4 ? 3 : 2) void attn32_kernel(cons
     for (int bb = 0; bb < 2; ++bb)
 #pragma unroll
       for (int v = 0; v < 16; v += 2) {
-        if (ABL & 2) continue;
         const float e0 = __builtin_amdgcn_exp2f(fmaf(sacc[bb][v], scl, nm));
         const float e1 = __builtin_amdgcn_exp2f(fmaf(sacc[bb][v + 1], scl, nm));
         sacc[bb][v] = e0;
@@ -600,7 +598,7 @@ __global__ __launch_bounds__(64 * NWV, NWV == 4 ? 3 : 2) void attn32_kernel(cons
           oacc[db] = mfma32<DT>(vf, pf[bb][s2], oacc[db]);
         }
 
-    if (!(ABL & 1) && t + 1 < ntiles) store_tile(s ^ 1);
+    if (t + 1 < ntiles) store_tile(s ^ 1);
     __syncthreads();
   };
 
@@ -933,59 +931,14 @@ __global__ __launch_bounds__(256, 2) void attn64_kernel(const cv_attn_params p) 
 extern "C" int cv_attention(const cv_attn_params* pp, void* stream) {
   if (!pp) return CV_ERR_ARG;
   cv_attn_params p = *pp;
-  if (p.q_hs == 0) p.q_hs = 64;
-  if (p.k_hs == 0) p.k_hs = 64;
-  if ((p.q_hs & 7) || (p.k_hs & 7)) return CV_ERR_ARG;
-  if (p.dtype != CV_BF16 && p.dtype != CV_F16) return CV_ERR_UNSUPPORTED;
-  if (p.B <= 0 || p.H <= 0 || p.Hkv <= 0 || (p.H % p.Hkv) || p.Tq <= 0 || p.Tk <= 0 || p.q_off < 0) return CV_ERR_ARG;
-  if (!p.q || !p.k || !p.vt || !p.out) return CV_ERR_ARG;
-  if ((p.ldq & 7) || (p.ldk & 7) || (p.vt_ld & 7) || (p.ldo & 3) || (p.q_bs & 7) || (p.k_bs & 7) || (p.o_bs & 3)) return CV_ERR_ARG;
-  if (p.vt_ld < p.Tk) return CV_ERR_ARG;
-  if ((int64_t)p.Tk * p.ldk * 2 >= (int64_t)1 << 31 || (int64_t)64 * p.vt_ld * 2 >= (int64_t)1 << 31) return CV_ERR_UNSUPPORTED;   // 32-bit buffer offsets per (batch, head)
-  if (((uintptr_t)p.q & 15) || ((uintptr_t)p.k & 15) || ((uintptr_t)p.vt & 15) || ((uintptr_t)p.out & 7)) return CV_ERR_ARG;
-  // p.mfma selects among the three forms (all tested against torch, tests/test_attention_gpu.py):
-  //   0 / 16 the 16x16x32 form above (the library's choice);
-  //   32 the same tiling on 32x32x16 MFMAs (half the MFMA issue slots, one cross-lane step per row max): 58.2 vs 57.0 us;
-  //   64 64 queries per wave, K / V^T by LDS-DMA into a 3-stage ring, the softmax of one query block issued between the MFMAs of the
-  //      other (no bias operand): 57.0 - 58.2 us.
-  // At the estimator's batch-8 shape (16 x 8 heads x T = 1000) all three take 57 - 58 us: the time is ~410 VALU + 32 MFMA issued per 64
-  // queries x 64 keys (SQ_INSTS_VALU identical in every form) and ~30 % of wave cycles waiting, not the tile schedule.
-  const int mf = p.mfma;
-  if (mf != 0 && mf != 16 && mf != 32 && mf != 64) return CV_ERR_ARG;
-  if (p.waves != 0 && p.waves != 2 && p.waves != 4) return CV_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  const size_t lds = 2 * STAGE_BYTES;
-  // 64-query workgroups when 128-query ones would not even fill the chip once (p.waves = 2 | 4 overrides: tuning aid)
-  const int64_t wgs4 = (int64_t)p.H * ((p.Tq + 127) / 128) * p.B;
-  const bool two = p.waves == 2 || (p.waves != 4 && wgs4 < 256);
-  if (!p.bias && p.Tk >= 8 && p.vt_ld >= 8 && mf == 64) {
-    dim3 grid(p.H, (p.Tq + 255) / 256, p.B);
-    const size_t lds64 = 3 * STAGE_BYTES;
-    if (p.dtype == CV_BF16) hipLaunchKernelGGL((attn64_kernel<CV_BF16>), grid, dim3(256), lds64, st, p);
-    else hipLaunchKernelGGL((attn64_kernel<CV_F16>), grid, dim3(256), lds64, st, p);
-    CV_CHECK_LAUNCH();
-    return CV_OK;
-  }
-  const bool m32 = mf == 32;
-  if (two) {
-    dim3 grid(p.H, (p.Tq + 63) / 64, p.B);
-    if (m32) {
-      if (p.dtype == CV_BF16) hipLaunchKernelGGL((attn32_kernel<CV_BF16, 2>), grid, dim3(128), lds, st, p);
-      else hipLaunchKernelGGL((attn32_kernel<CV_F16, 2>), grid, dim3(128), lds, st, p);
-    } else {
-      if (p.dtype == CV_BF16) hipLaunchKernelGGL((attn_kernel<CV_BF16, 2>), grid, dim3(128), lds, st, p);
-      else hipLaunchKernelGGL((attn_kernel<CV_F16, 2>), grid, dim3(128), lds, st, p);
-    }
-  } else {
-    dim3 grid(p.H, (p.Tq + 127) / 128, p.B);
-    if (m32) {
-      if (p.dtype == CV_BF16) hipLaunchKernelGGL((attn32_kernel<CV_BF16, 4>), grid, dim3(256), lds, st, p);
-      else hipLaunchKernelGGL((attn32_kernel<CV_F16, 4>), grid, dim3(256), lds, st, p);
-    } else {
-      if (p.dtype == CV_BF16) hipLaunchKernelGGL((attn_kernel<CV_BF16, 4>), grid, dim3(256), lds, st, p);
-      else hipLaunchKernelGGL((attn_kernel<CV_F16, 4>), grid, dim3(256), lds, st, p);
-    }
-  }
+  AttnSel s;
+  if (int rc = attn_select(p, &s)) return rc;
+  void (*k)(const cv_attn_params) = nullptr;
+  with_dt16(p.dtype, [&](auto DT) {
+    if (s.form == 64) k = attn64_kernel<DT()>;
+    else with_value<2, 4>(s.waves, [&](auto NWV) { k = s.form == 32 ? attn32_kernel<DT(), NWV()> : attn_kernel<DT(), NWV()>; });
+  });
+  hipLaunchKernelGGL(k, dim3(s.grid_x, s.grid_y, s.grid_z), dim3(s.block), s.lds, (hipStream_t)stream, p);
   CV_CHECK_LAUNCH();
   return CV_OK;
 }

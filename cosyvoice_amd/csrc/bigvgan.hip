@@ -11,17 +11,6 @@ constexpr int XH = 7;            // x halo on each side
 constexpr int NU = 2 * TT + 11;  // upsampled values needed: n' in [2 t0 - 5, 2 t0 + 2 TT + 5]
 
 template <int DT>
-__device__ __forceinline__ float ld(const void* p, int64_t i) {
-  if constexpr (DT == CV_F32) return ((const float*)p)[i];
-  else return Elem16<DT>::to_f32(((const uint16_t*)p)[i]);
-}
-template <int DT>
-__device__ __forceinline__ void stv(void* p, int64_t i, float v) {
-  if constexpr (DT == CV_F32) ((float*)p)[i] = v;
-  else ((uint16_t*)p)[i] = Elem16<DT>::from_f32(v);
-}
-
-template <int DT>
 __global__ __launch_bounds__(256) void anti_alias_kernel(const void* x, void* y, int C, int T, const float* upf, const float* dnf,
                                                          const float* alog, const float* blog) {
   __shared__ float sx[TT + 2 * XH];
@@ -34,7 +23,7 @@ __global__ __launch_bounds__(256) void anti_alias_kernel(const void* x, void* y,
   if (tid < 12) sf[tid] = upf[tid];
   else if (tid < 24) sf[tid] = dnf[tid - 12];
   // x[t0 - XH .. t0 + TT + XH) with replicate clamping (= the replicate pad of UpSample1d, resample.py:30)
-  for (int i = tid; i < TT + 2 * XH; i += 256) sx[i] = ld<DT>(x, row + min(max(t0 - XH + i, 0), T - 1));
+  for (int i = tid; i < TT + 2 * XH; i += 256) sx[i] = load_as<DT>(x, row + min(max(t0 - XH + i, 0), T - 1));
   __syncthreads();
   const float alpha = __expf(alog[c]);
   const float inv_beta = 1.0f / (__expf(blog[c]) + 1e-9f);
@@ -61,7 +50,7 @@ __global__ __launch_bounds__(256) void anti_alias_kernel(const void* x, void* y,
     float acc = 0.f;
 #pragma unroll
     for (int k = 0; k < 12; ++k) acc += su[2 * tid + k] * sf[12 + k];
-    stv<DT>(y, row + t, acc);
+    store_as<DT>(y, row + t, acc);
   }
 }
 
@@ -85,7 +74,7 @@ __global__ __launch_bounds__(256) void anti_alias_cl_kernel(const void* x, int l
   else if (tid < 24) sf[tid] = dnf[tid - 12];
   for (int i = tr; i < CT + 2 * CXH; i += 4) {
     const int t = min(max(t0 - CXH + i, 0), T - 1);  // replicate pad of UpSample1d (resample.py:30)
-    sx[i][cl] = ld<IDT>(x, ((int64_t)b * T + t) * ldx + cc);
+    sx[i][cl] = load_as<IDT>(x, ((int64_t)b * T + t) * ldx + cc);
   }
   const float alpha = __expf(alog[cc]);
   const float inv_beta = 1.0f / (__expf(blog[cc]) + 1e-9f);
@@ -114,7 +103,7 @@ __global__ __launch_bounds__(256) void anti_alias_cl_kernel(const void* x, int l
     float acc = 0.f;
 #pragma unroll
     for (int k = 0; k < 12; ++k) acc += su[2 * tt + k][cl] * sf[12 + k];
-    stv<ODT>(y, ((int64_t)b * T + t) * ldy + c, acc);
+    store_as<ODT>(y, ((int64_t)b * T + t) * ldy + c, acc);
   }
 }
 
@@ -126,12 +115,9 @@ extern "C" int cv_anti_alias_act(const void* x, void* y, int32_t dtype, int32_t 
   if (C > 65535 || B > 65535) return CV_ERR_ARG;
   dim3 grid((T + TT - 1) / TT, C, B);
   hipStream_t st = (hipStream_t)stream;
-  switch (dtype) {
-    case CV_F32: hipLaunchKernelGGL(anti_alias_kernel<CV_F32>, grid, dim3(256), 0, st, x, y, C, T, up_filter, down_filter, alpha_log, beta_log); break;
-    case CV_BF16: hipLaunchKernelGGL(anti_alias_kernel<CV_BF16>, grid, dim3(256), 0, st, x, y, C, T, up_filter, down_filter, alpha_log, beta_log); break;
-    case CV_F16: hipLaunchKernelGGL(anti_alias_kernel<CV_F16>, grid, dim3(256), 0, st, x, y, C, T, up_filter, down_filter, alpha_log, beta_log); break;
-    default: return CV_ERR_ARG;
-  }
+  if (!with_dt(dtype, [&](auto DT) {
+        hipLaunchKernelGGL(anti_alias_kernel<DT()>, grid, dim3(256), 0, st, x, y, C, T, up_filter, down_filter, alpha_log, beta_log);
+      })) return CV_ERR_ARG;
   CV_CHECK_LAUNCH();
   return CV_OK;
 }
@@ -143,20 +129,12 @@ extern "C" int cv_anti_alias_act_cl(const void* x, int32_t ldx, int32_t in_dtype
   if (B > 65535) return CV_ERR_ARG;
   dim3 grid((T + CT - 1) / CT, (C + 63) / 64, B);
   hipStream_t st = (hipStream_t)stream;
-#define AA_OUT(IDT_)                                                                                                              \
-  switch (out_dtype) {                                                                                                            \
-    case CV_F32: hipLaunchKernelGGL((anti_alias_cl_kernel<IDT_, CV_F32>), grid, dim3(256), 0, st, x, ldx, y, ldy, T, C, up_filter, down_filter, alpha_log, beta_log); break;  \
-    case CV_BF16: hipLaunchKernelGGL((anti_alias_cl_kernel<IDT_, CV_BF16>), grid, dim3(256), 0, st, x, ldx, y, ldy, T, C, up_filter, down_filter, alpha_log, beta_log); break; \
-    case CV_F16: hipLaunchKernelGGL((anti_alias_cl_kernel<IDT_, CV_F16>), grid, dim3(256), 0, st, x, ldx, y, ldy, T, C, up_filter, down_filter, alpha_log, beta_log); break;  \
-    default: return CV_ERR_ARG;                                                                                                   \
-  }
-  switch (in_dtype) {
-    case CV_F32: AA_OUT(CV_F32); break;
-    case CV_BF16: AA_OUT(CV_BF16); break;
-    case CV_F16: AA_OUT(CV_F16); break;
-    default: return CV_ERR_ARG;
-  }
-#undef AA_OUT
+  bool out_ok = false;
+  if (!with_dt(in_dtype, [&](auto IDT) {
+        out_ok = with_dt(out_dtype, [&](auto ODT) {
+          hipLaunchKernelGGL((anti_alias_cl_kernel<IDT(), ODT()>), grid, dim3(256), 0, st, x, ldx, y, ldy, T, C, up_filter, down_filter, alpha_log, beta_log);
+        });
+      }) || !out_ok) return CV_ERR_ARG;
   CV_CHECK_LAUNCH();
   return CV_OK;
 }

@@ -3,11 +3,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <atomic>
+#include <type_traits>
 #include "../../include/cosyvoice_amd.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
 typedef __attribute__((ext_vector_type(4))) float f32x4_t;
+typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+
+constexpr float NEG_BIG = -1e30f;   // masked attention scores / running maxima: large, finite (no NaN is ever formed)
 
 #define CV_CHECK_LAUNCH()                                  \
   do {                                                     \
@@ -26,6 +30,15 @@ struct PerDeviceOnce {
     if (!done[dev].load(std::memory_order_acquire)) { f(); done[dev].store(true, std::memory_order_release); }
   }
 };
+
+// Host side: a run-time value -> template argument.  f(std::integral_constant<int, V>{}) runs for the V of Vs... that equals v;
+// false = none does, and the CALLER returns its own status code.  with_dt16 / with_dt: the element types an entry point takes.
+template <int... Vs, typename F>
+bool with_value(int v, F&& f) { return ((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...); }
+template <typename F> bool with_dt16(int dtype, F&& f) { return with_value<CV_BF16, CV_F16>(dtype, f); }
+template <typename F> bool with_dt(int dtype, F&& f) { return with_value<CV_F32, CV_BF16, CV_F16>(dtype, f); }
+// Host side: grid of an elementwise grid-stride kernel, 256 threads per block, at most 8192 blocks
+inline int blocks_of_256(int64_t n) { const int64_t b = (n + 255) / 256; return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b)); }
 
 template <typename To, typename From>
 __device__ __forceinline__ To bitcast(const From& f) {
@@ -56,6 +69,28 @@ __device__ __forceinline__ uint32_t pack2(float a, float b) {
   const f32x2_t v = f32x2_t{a, b};
   if constexpr (DT == CV_BF16) return bitcast<uint32_t>(__builtin_convertvector(v, bf16x2_t));
   else return bitcast<uint32_t>(__builtin_convertvector(v, f16x2_t));
+}
+
+template <int DT>
+__device__ __forceinline__ uint2 pack4(float a, float b, float c, float d) {
+  return make_uint2(pack2<DT>(a, b), pack2<DT>(c, d));
+}
+
+// ---- element i of a DT array (fp32, or 16-bit with RNE) from / to fp32; store4_as: four consecutive elements, i % 4 == 0
+template <int DT>
+__device__ __forceinline__ float load_as(const void* p, int64_t i) {
+  if constexpr (DT == CV_F32) return ((const float*)p)[i];
+  else return Elem16<DT>::to_f32(((const uint16_t*)p)[i]);
+}
+template <int DT>
+__device__ __forceinline__ void store_as(void* base, int64_t i, float v) {
+  if constexpr (DT == CV_F32) ((float*)base)[i] = v;
+  else ((uint16_t*)base)[i] = Elem16<DT>::from_f32(v);
+}
+template <int DT>
+__device__ __forceinline__ void store4_as(void* base, int64_t i, float a, float b, float c, float d) {
+  if constexpr (DT == CV_F32) *(float4*)((float*)base + i) = make_float4(a, b, c, d);
+  else *(uint2*)((uint16_t*)base + i) = pack4<DT>(a, b, c, d);
 }
 
 // One "block" MFMA step over the K extent of four 16-byte chunks (32 k for 16-bit, 16 k for f32).

@@ -45,7 +45,6 @@ constexpr int NW = 8;         // waves per workgroup (two per SIMD)
 constexpr int NTHR = 64 * NW;
 constexpr int NS = 4;         // ring slots per wave, 8 fragments (8 KiB per wave) each
 constexpr int HC = 32 * NW;   // hidden columns per FFN chunk: two 16-column tiles per wave
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
 
 // 16-byte chunk slot of (row, chunk) in an operand image whose rows hold >= 16 chunks: XOR the low 4 chunk bits with row & 15.
@@ -92,11 +91,6 @@ __device__ __forceinline__ void pin_regs(V (&v)[N]) {
   else if constexpr (N == 6) PIN6(v);
   else if constexpr (N == 4) PIN4(v);
   else PIN2(v);
-}
-
-template <int DT>
-__device__ __forceinline__ uint2 pack4(float a, float b, float c, float d) {
-  return make_uint2(pack2<DT>(a, b), pack2<DT>(c, d));
 }
 
 // sum over the 16 lanes of a DPP row (lanes 16 g .. 16 g + 15), every lane gets the total: 4 v_add_f32_dpp, no LDS crossbar
@@ -176,14 +170,11 @@ __device__ __forceinline__ void head_ld(uint4 (&sl)[8], const __amdgpu_buffer_rs
 
 // The head's GEMM + stores over the 16 MT-row operand image at `img` (LayerNorm output, 512-byte rows).  On entry ring slots 0..3 hold
 // fragment groups 0..3 (head_ld) and the image is complete (barrier passed).
-template <int DT, int MT, int ABL>
+template <int DT, int MT>
 __device__ __forceinline__ void head_body(const cv_tblock_params& p, const char* img, uint4 (&s)[NS][8], const __amdgpu_buffer_rsrc_t w_rs,
                                           int lane16, int wid, int lq, int lg, int r, int t0) {
   constexpr int NSTEP = 3 * TB_INNER / 16 / (4 * NW);  // 96 tiles / (8 waves x 4 tiles) = 3
-  auto ld = [&](uint4 (&sl)[8], int G) {
-    if ((ABL & 2) && G >= NS) return;
-    head_ld(sl, w_rs, lane16, wid, G);
-  };
+  auto ld = [&](uint4 (&sl)[8], int G) { head_ld(sl, w_rs, lane16, wid, G); };
   f32x4_t acc[MT][4];
   auto compute = [&](uint4 (&sl)[8], int kq, bool vpart) {
 #pragma unroll
@@ -236,11 +227,6 @@ __device__ __forceinline__ void head_body(const cv_tblock_params& p, const char*
           const uint2 u = pack4<DT>(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
           w[j][0] = u.x; w[j][1] = u.y;
         }
-        if (ABL & 1) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) asm volatile("" :: "v"(w[j][0]), "v"(w[j][1]));
-          continue;
-        }
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
           const auto a = __builtin_amdgcn_permlane32_swap(w[0][k], w[2][k], false, false);
@@ -266,7 +252,6 @@ __device__ __forceinline__ void head_body(const cv_tblock_params& p, const char*
           const int t = t0 + 16 * i + 4 * lg;
           const uint2 u = pack4<DT>(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
           const int off = (vrow * p.vt_ld + t) * 2;
-          if (ABL & 1) { asm volatile("" :: "v"(u.x), "v"(u.y)); continue; }
           __builtin_amdgcn_raw_buffer_store_b64(u32x2_t{u.x, u.y}, vt_rs, (t + 3 < p.T) ? off : 0x7FFFFFF0, 0, 0);
         }
       }
@@ -289,7 +274,7 @@ __device__ __forceinline__ void head_body(const cv_tblock_params& p, const char*
   }
 }
 
-template <int DT, int MT, int ABL = 0>   // ABL: timing-only ablations, wrong results, instantiated by hand for a measurement ("Timing ablations"; 1: no output stores, 2: no ring refills)
+template <int DT, int MT>
 __global__ __launch_bounds__(NTHR, 2) void tblock_head_kernel(const cv_tblock_params p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -306,7 +291,7 @@ __global__ __launch_bounds__(NTHR, 2) void tblock_head_kernel(const cv_tblock_pa
   head_ld(s[2], w_rs, lane16, wid, 2);
   head_ld(s[3], w_rs, lane16, wid, 3);
   __syncthreads();
-  head_body<DT, MT, ABL>(p, smem, s, w_rs, lane16, wid, lq, lg, r, t0);
+  head_body<DT, MT>(p, smem, s, w_rs, lane16, wid, lq, lg, r, t0);
 }
 
 template <int MT>
@@ -326,7 +311,7 @@ __device__ __forceinline__ void ln_acc(f32x4_t (&acc)[MT][2], float* red, const 
 // image, and the [Q | K | V^T] GEMM of head_body runs on it — the last FFN refills of the register ring already fetch the head's first
 // weight groups.  One launch and one 1 KB-per-row read of x less per block; the head fields of the parameter block (g1, b1n, wqkv_p, qk,
 // vt) then describe block i + 1.  LDS: two more staged vectors (g1 | b1n) behind the four of the tail.
-template <int DT, bool OUTPROJ, int MT, int ABL = 0, bool NEXT = false>   // ABL: timing-only ablations, wrong results, instantiated by hand for a measurement ("Timing ablations"; 1: GELU -> identity, 2: no ring refills)
+template <int DT, bool OUTPROJ, int MT, bool NEXT = false>
 __global__ __launch_bounds__(NTHR, 2) void tblock_tail_kernel(const cv_tblock_params p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* ximg = smem;
@@ -354,7 +339,6 @@ __global__ __launch_bounds__(NTHR, 2) void tblock_tail_kernel(const cv_tblock_pa
   uint4 s[NS][8];
   const __amdgpu_buffer_rsrc_t wh_rs = frag_rsrc(NEXT ? p.wqkv_p : p.w1_p, NEXT ? 96 * (TB_C / 32) : 64 * 8);   // NEXT: the following head's weights
   auto ld_ffn = [&](uint4 (&sl)[8], int f) {   // FFN group f = 4 c + q (clamped to the last chunk: harmless re-reads at the end)
-    if ((ABL & 2) && f >= NS) return;
     if constexpr (NEXT) {
       if (f >= 4 * NC) { head_ld(sl, wh_rs, lane16, wid, f - 4 * NC); return; }   // ring slot f % 4 = head group f - 16 (its k-quarter)
     }
@@ -555,7 +539,6 @@ __global__ __launch_bounds__(NTHR, 2) void tblock_tail_kernel(const cv_tblock_pa
       for (int j = 0; j < 2; ++j) {
         const int ch = (2 * wid + j) * 2 + (lg >> 1);
         *(uint2*)(hb + m * 512 + (swz16(m, ch) << 4) + ((lg & 1) << 3)) =
-            (ABL & 1) ? pack4<DT>(acc1[i][j][0], acc1[i][j][1], acc1[i][j][2], acc1[i][j][3]) :
             pack4<DT>(gelu_erf(acc1[i][j][0]), gelu_erf(acc1[i][j][1]), gelu_erf(acc1[i][j][2]), gelu_erf(acc1[i][j][3]));
       }
     }
@@ -604,7 +587,7 @@ __global__ __launch_bounds__(NTHR, 2) void tblock_tail_kernel(const cv_tblock_pa
       }
     }
     __syncthreads();
-    head_body<DT, MT, 0>(p, ximg, s, wh_rs, lane16, wid, lq, lg, r, t0);
+    head_body<DT, MT>(p, ximg, s, wh_rs, lane16, wid, lq, lg, r, t0);
   }
 }
 
@@ -849,22 +832,32 @@ int check_common(const cv_tblock_params& p) {
   if (p.R <= 0 || p.T <= 0 || !p.x || (p.ldx & 3) || ((uintptr_t)p.x & 15) || p.mt < 0 || p.mt > 4) return CV_ERR_ARG;
   return CV_OK;
 }
+int check_head_fields(const cv_tblock_params& p) {
+  if (!p.g1 || !p.b1n || !p.wqkv_p || !p.qk || !p.vt) return CV_ERR_ARG;
+  if ((p.ldqk & 7) || (p.vt_ld & 3) || p.vt_ld < p.T || ((uintptr_t)p.qk & 15) || ((uintptr_t)p.vt & 7) || ((uintptr_t)p.wqkv_p & 15))
+    return CV_ERR_ARG;   // [Q | K] rows are written with 16-byte stores
+  if ((int64_t)p.T * p.ldqk * 2 >= (1ll << 31) || (int64_t)TB_INNER * p.vt_ld * 2 >= 0x7FFFFFF0ll) return CV_ERR_ARG;   // 32-bit buffer offsets
+  return CV_OK;
+}
+int check_tail_fields(const cv_tblock_params& p, bool need_outproj) {
+  if (!p.g3 || !p.b3n || !p.w1_p || !p.bf1 || !p.w2_p || !p.bf2) return CV_ERR_ARG;
+  if (((uintptr_t)p.w1_p & 15) || ((uintptr_t)p.w2_p & 15) || ((uintptr_t)p.bf1 & 15)) return CV_ERR_ARG;
+  if (p.out_act && ((p.ldoa & 3) || ((uintptr_t)p.out_act & 7))) return CV_ERR_ARG;
+  if (need_outproj && !p.ao) return CV_ERR_ARG;
+  if (p.ao && (!p.wo_p || !p.bo || (p.ldao & 7) || ((uintptr_t)p.ao & 15) || ((uintptr_t)p.wo_p & 15))) return CV_ERR_ARG;
+  return CV_OK;
+}
 
 template <typename K>
 void set_lds(K kern, size_t lds) { hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); }
 
 constexpr size_t TAIL_LDS = 98304 + 4096 + 4096 + 4096 + 2048;
-template <int DT, bool OP, int MT, int ABL, bool NEXT = false>
+template <int DT, bool OP, int MT, bool NEXT>
 void launch_tail(const cv_tblock_params& p, hipStream_t st) {
   static PerDeviceOnce once;   // > 64 KiB of dynamic LDS needs the opt-in
-  once.run([] { set_lds(tblock_tail_kernel<DT, OP, MT, ABL, NEXT>, TAIL_LDS); });
+  once.run([] { set_lds(tblock_tail_kernel<DT, OP, MT, NEXT>, TAIL_LDS); });
   dim3 grid((p.T + 16 * MT - 1) / (16 * MT), p.R);
-  hipLaunchKernelGGL((tblock_tail_kernel<DT, OP, MT, ABL, NEXT>), grid, dim3(NTHR), TAIL_LDS, st, p);
-}
-template <int DT, int MT, int ABL>
-void launch_head(const cv_tblock_params& p, hipStream_t st) {
-  dim3 grid((p.T + 16 * MT - 1) / (16 * MT), p.R);
-  hipLaunchKernelGGL((tblock_head_kernel<DT, MT, ABL>), grid, dim3(NTHR), 32768, st, p);
+  hipLaunchKernelGGL((tblock_tail_kernel<DT, OP, MT, NEXT>), grid, dim3(NTHR), TAIL_LDS, st, p);
 }
 // rows per tile (16 MT, MT = 1 .. 4): the one that minimises (rounds of workgroups over the CUs the launch may use) x (time of one
 // workgroup); one workgroup per CU is resident.  A workgroup's time is NOT proportional to its rows: every workgroup streams the block's
@@ -897,17 +890,10 @@ auto with_mt(int mt, F&& f) {
     default: return f(std::integral_constant<int, 4>{});
   }
 }
-template <int DT>
-void dispatch_head(const cv_tblock_params& p, hipStream_t st) {
-  with_mt(pick_mt(p.R, p.T, p.cus, p.mt), [&](auto mt) { launch_head<DT, mt(), 0>(p, st); });
-}
-template <int DT>
-void dispatch_tail_head(const cv_tblock_params& p, hipStream_t st) {
-  with_mt(pick_mt(p.R, p.T, p.cus, p.mt), [&](auto mt) { launch_tail<DT, true, mt(), 0, true>(p, st); });
-}
-template <int DT, bool OP>
+// the tail in its three forms: OP = with the attention out-projection, NEXT = followed by the next block's head (then OP as well)
+template <bool OP, bool NEXT>
 void dispatch_tail(const cv_tblock_params& p, hipStream_t st) {
-  with_mt(pick_mt(p.R, p.T, p.cus, p.mt), [&](auto mt) { launch_tail<DT, OP, mt(), 0>(p, st); });
+  with_dt16(p.dtype, [&](auto DT) { with_mt(pick_mt(p.R, p.T, p.cus, p.mt), [&](auto mt) { launch_tail<DT(), OP, mt(), NEXT>(p, st); }); });
 }
 
 }  // namespace
@@ -918,13 +904,13 @@ extern "C" int cv_tblock_head(const cv_tblock_params* pp, void* stream) {
   if (!pp) return CV_ERR_ARG;
   const cv_tblock_params p = *pp;
   if (int rc = check_common(p)) return rc;
-  if (!p.g1 || !p.b1n || !p.wqkv_p || !p.qk || !p.vt) return CV_ERR_ARG;
-  if ((p.ldqk & 7) || (p.vt_ld & 3) || p.vt_ld < p.T || ((uintptr_t)p.qk & 15) || ((uintptr_t)p.vt & 7) || ((uintptr_t)p.wqkv_p & 15))
-    return CV_ERR_ARG;   // [Q | K] rows are written with 16-byte stores
-  if ((int64_t)p.T * p.ldqk * 2 >= (1ll << 31) || (int64_t)TB_INNER * p.vt_ld * 2 >= 0x7FFFFFF0ll) return CV_ERR_ARG;   // 32-bit buffer offsets
-  hipStream_t st = (hipStream_t)stream;
-  if (p.dtype == CV_BF16) dispatch_head<CV_BF16>(p, st);
-  else dispatch_head<CV_F16>(p, st);
+  if (int rc = check_head_fields(p)) return rc;
+  with_dt16(p.dtype, [&](auto DT) {
+    with_mt(pick_mt(p.R, p.T, p.cus, p.mt), [&](auto mt) {
+      dim3 grid((p.T + 16 * mt() - 1) / (16 * mt()), p.R);
+      hipLaunchKernelGGL((tblock_head_kernel<DT(), mt()>), grid, dim3(NTHR), 32768, (hipStream_t)stream, p);
+    });
+  });
   CV_CHECK_LAUNCH();
   return CV_OK;
 }
@@ -933,14 +919,9 @@ extern "C" int cv_tblock_tail(const cv_tblock_params* pp, void* stream) {
   if (!pp) return CV_ERR_ARG;
   const cv_tblock_params p = *pp;
   if (int rc = check_common(p)) return rc;
-  if (!p.g3 || !p.b3n || !p.w1_p || !p.bf1 || !p.w2_p || !p.bf2) return CV_ERR_ARG;
-  if (((uintptr_t)p.w1_p & 15) || ((uintptr_t)p.w2_p & 15) || ((uintptr_t)p.bf1 & 15)) return CV_ERR_ARG;
-  if (p.out_act && ((p.ldoa & 3) || ((uintptr_t)p.out_act & 7))) return CV_ERR_ARG;
-  const bool outproj = p.ao != nullptr;
-  if (outproj && (!p.wo_p || !p.bo || (p.ldao & 7) || ((uintptr_t)p.ao & 15) || ((uintptr_t)p.wo_p & 15))) return CV_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  if (p.dtype == CV_BF16) { if (outproj) dispatch_tail<CV_BF16, true>(p, st); else dispatch_tail<CV_BF16, false>(p, st); }
-  else { if (outproj) dispatch_tail<CV_F16, true>(p, st); else dispatch_tail<CV_F16, false>(p, st); }
+  if (int rc = check_tail_fields(p, false)) return rc;
+  if (p.ao) dispatch_tail<true, false>(p, (hipStream_t)stream);
+  else dispatch_tail<false, false>(p, (hipStream_t)stream);
   CV_CHECK_LAUNCH();
   return CV_OK;
 }
@@ -950,18 +931,11 @@ extern "C" int cv_tblock_tail_head(const cv_tblock_params* pp, void* stream) {
   if (!pp) return CV_ERR_ARG;
   const cv_tblock_params p = *pp;
   if (int rc = check_common(p)) return rc;
-  if (!p.g3 || !p.b3n || !p.w1_p || !p.bf1 || !p.w2_p || !p.bf2 || !p.ao || !p.wo_p || !p.bo) return CV_ERR_ARG;
-  if (((uintptr_t)p.w1_p & 15) || ((uintptr_t)p.w2_p & 15) || ((uintptr_t)p.bf1 & 15) || (p.ldao & 7) || ((uintptr_t)p.ao & 15) || ((uintptr_t)p.wo_p & 15))
-    return CV_ERR_ARG;
   if (p.out_act) return CV_ERR_ARG;   // the 16-bit copy belongs to the LAST block of a group, which has no following head
-  if (!p.g1 || !p.b1n || !p.wqkv_p || !p.qk || !p.vt) return CV_ERR_ARG;
-  if ((p.ldqk & 7) || (p.vt_ld & 3) || p.vt_ld < p.T || ((uintptr_t)p.qk & 15) || ((uintptr_t)p.vt & 7) || ((uintptr_t)p.wqkv_p & 15))
-    return CV_ERR_ARG;
-  if ((int64_t)p.T * p.ldqk * 2 >= (1ll << 31) || (int64_t)TB_INNER * p.vt_ld * 2 >= 0x7FFFFFF0ll || (int64_t)p.T * p.ldx * 4 >= (1ll << 31))
-    return CV_ERR_ARG;   // 32-bit buffer offsets
-  hipStream_t st = (hipStream_t)stream;
-  if (p.dtype == CV_BF16) dispatch_tail_head<CV_BF16>(p, st);
-  else dispatch_tail_head<CV_F16>(p, st);
+  if (int rc = check_tail_fields(p, true)) return rc;
+  if (int rc = check_head_fields(p)) return rc;
+  if ((int64_t)p.T * p.ldx * 4 >= (1ll << 31)) return CV_ERR_ARG;   // 32-bit buffer offsets
+  dispatch_tail<true, true>(p, (hipStream_t)stream);
   CV_CHECK_LAUNCH();
   return CV_OK;
 }
@@ -983,7 +957,9 @@ template <int STAGE>
 int dispatch_resblock(const cv_resblock_params& p, hipStream_t st) {
   // tile-size choice shared with the transformer-block kernels
   return with_mt(pick_mt(p.R, p.T, p.cus, p.mt), [&](auto mt) {
-    return p.dtype == CV_BF16 ? launch_resblock<CV_BF16, STAGE, mt()>(p, st) : launch_resblock<CV_F16, STAGE, mt()>(p, st);
+    int rc = CV_ERR_UNSUPPORTED;
+    with_dt16(p.dtype, [&](auto DT) { rc = launch_resblock<DT(), STAGE, mt()>(p, st); });
+    return rc;
   });
 }
 int check_resblock(const cv_resblock_params& p, int stage) {

@@ -15,7 +15,6 @@
 
 namespace {
 
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 
 template <int DT> struct ElemSize { static constexpr int value = (DT == CV_F32) ? 4 : 2; };
 
@@ -25,27 +24,6 @@ template <int DT> struct ElemSize { static constexpr int value = (DT == CV_F32) 
 //  * the MFMA fragment read (lane = row l&15, chunk ks*4 + (l>>4)) hits 16 distinct slots per ds_read_b128 lane group.
 __device__ __forceinline__ int lds_chunk_off(int row, int kc) {
   return (row << 7) + ((kc ^ ((row >> 1) & 7)) << 4);
-}
-
-template <int DT>
-__device__ __forceinline__ void store_act(void* base, int64_t idx, float v) {
-  if constexpr (DT == CV_F32) {
-    ((float*)base)[idx] = v;
-  } else {
-    ((uint16_t*)base)[idx] = Elem16<DT>::from_f32(v);
-  }
-}
-
-template <int DT>
-__device__ __forceinline__ void store_act4(void* base, int64_t idx, float a, float b, float c, float d) {
-  if constexpr (DT == CV_F32) {
-    *(float4*)((float*)base + idx) = make_float4(a, b, c, d);
-  } else {
-    uint2 u;
-    u.x = pack2<DT>(a, b);
-    u.y = pack2<DT>(c, d);
-    *(uint2*)((uint16_t*)base + idx) = u;
-  }
 }
 
 // fp32 values in the PRE-SPLIT storage of the bf16x3 path: every aligned group of 8 values (32 bytes) holds [8 x bf16 hi | 8 x bf16 lo]
@@ -147,7 +125,7 @@ __device__ __forceinline__ void gemm_epilogue(const cv_gemm_params& p, f32x4_t (
               *(uint4*)(oact + (idx & ~(int64_t)7) * 4 + ((idx >> 2) & 1) * 16) = make_uint4(s0[0], s1[0], s0[1], s1[1]);
             }
           } else if (live) {
-            store_act4<DT>(oact, (int64_t)orow[i] * p.ldoa + nbj[j], a0, a1, a2, a3);
+            store4_as<DT>(oact, (int64_t)orow[i] * p.ldoa + nbj[j], a0, a1, a2, a3);
           }
         }
       }
@@ -183,16 +161,16 @@ __device__ __forceinline__ void gemm_epilogue(const cv_gemm_params& p, f32x4_t (
       if (p.out_mode == CV_OUT_QKV) {
         // 16-bit outputs only; boundaries are multiples of 64 so a 4-group never straddles
         if (nb < p.q_cols) {
-          store_act4<DT>(oact, (int64_t)orow * p.ldoa + nb, v[0] * p.q_scale, v[1] * p.q_scale, v[2] * p.q_scale, v[3] * p.q_scale);
+          store4_as<DT>(oact, (int64_t)orow * p.ldoa + nb, v[0] * p.q_scale, v[1] * p.q_scale, v[2] * p.q_scale, v[3] * p.q_scale);
         } else if (nb < p.q_cols + p.k_cols) {
           char* kb = (char*)p.k_out + (int64_t)z * p.k_bs * ES;
-          store_act4<DT>(kb, (int64_t)orow * p.ldk + (nb - p.q_cols), v[0], v[1], v[2], v[3]);
+          store4_as<DT>(kb, (int64_t)orow * p.ldk + (nb - p.q_cols), v[0], v[1], v[2], v[3]);
         } else {
           const int c = nb - p.q_cols - p.k_cols;
           const int h = c >> 6, d = c & 63;
 #pragma unroll
           for (int r = 0; r < 4; ++r)
-            store_act<DT>(p.vt_out, ((int64_t)(z * p.vt_heads + h) * 64 + d + r) * p.vt_ld + orow, v[r]);
+            store_as<DT>(p.vt_out, ((int64_t)(z * p.vt_heads + h) * 64 + d + r) * p.vt_ld + orow, v[r]);
         }
         continue;
       }
@@ -206,7 +184,7 @@ __device__ __forceinline__ void gemm_epilogue(const cv_gemm_params& p, f32x4_t (
           const float g = (acc[i][j > 0 ? j - 1 : 0][r] + (p.bias ? p.bias[nb - 16 + r] : 0.f)) * p.out_scale;
           const float hval = act_silu(g) * v[r];
           if (o32) o32[(int64_t)orow * p.ldo32 + ncol + r] = hval;
-          if (oact) store_act<DT>(oact, (int64_t)orow * p.ldoa + ncol + r, hval);
+          if (oact) store_as<DT>(oact, (int64_t)orow * p.ldoa + ncol + r, hval);
         }
         continue;
       }
@@ -214,7 +192,7 @@ __device__ __forceinline__ void gemm_epilogue(const cv_gemm_params& p, f32x4_t (
       for (int r = 0; r < 4; ++r) {
         if (nb + r >= p.N) continue;
         if (o32) o32[(int64_t)orow * p.ldo32 + nb + r] = v[r];
-        if (oact) store_act<DT>(oact, (int64_t)orow * p.ldoa + nb + r, apply_act(p.act, v[r], ap[r], p.act_slope));
+        if (oact) store_as<DT>(oact, (int64_t)orow * p.ldoa + nb + r, apply_act(p.act, v[r], ap[r], p.act_slope));
       }
     }
   }
@@ -723,10 +701,7 @@ extern "C" int cv_gemm(const cv_gemm_params* pp, void* stream) {
   }
   hipStream_t st = (hipStream_t)stream;
   if (x3) return dispatch_x3(p, st);
-  switch (p.dtype) {
-    case CV_F32: return dispatch<CV_F32>(p, st);
-    case CV_BF16: return dispatch<CV_BF16>(p, st);
-    case CV_F16: return dispatch<CV_F16>(p, st);
-    default: return CV_ERR_ARG;
-  }
+  int rc = CV_ERR_ARG;
+  with_dt(p.dtype, [&](auto DT) { rc = dispatch<DT()>(p, st); });
+  return rc;
 }

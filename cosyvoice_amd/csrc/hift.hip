@@ -4,12 +4,6 @@
 
 namespace {
 
-template <int DT>
-__device__ __forceinline__ void st(void* base, int64_t i, float v) {
-  if constexpr (DT == CV_F32) ((float*)base)[i] = v;
-  else ((uint16_t*)base)[i] = Elem16<DT>::from_f32(v);
-}
-
 // ---- [B][C][T] fp32 -> [B][T][ldo] DT through a 32x33 LDS tile (coalesced on both sides)
 template <int DT>
 __global__ __launch_bounds__(256) void to_cl_kernel(const float* x, void* out, int C, int T, int ldo) {
@@ -23,7 +17,7 @@ __global__ __launch_bounds__(256) void to_cl_kernel(const float* x, void* out, i
   __syncthreads();
   for (int r = ty; r < 32; r += 8) {
     const int t = t0 + r, c = c0 + tx;
-    if (t < T && c < ldo) st<DT>(out, ((int64_t)b * T + t) * ldo + c, tile[tx][r]);
+    if (t < T && c < ldo) store_as<DT>(out, ((int64_t)b * T + t) * ldo + c, tile[tx][r]);
   }
 }
 
@@ -103,7 +97,7 @@ __global__ __launch_bounds__(256) void stft16_kernel(const float* s, void* out, 
   }
   if (f >= F) return;
   if (k >= 9) {
-    for (int c = 18 + (k - 9); c < ldo; c += 3) st<DT>(out, ob + c, 0.f);
+    for (int c = 18 + (k - 9); c < ldo; c += 3) store_as<DT>(out, ob + c, 0.f);
     return;
   }
   float re = 0.f, im = 0.f;
@@ -117,8 +111,8 @@ __global__ __launch_bounds__(256) void stft16_kernel(const float* s, void* out, 
     re += v * c_cos16[ph];
     im -= v * c_cos16[(ph + 12) & 15];  // sin(2 pi ph/16) = cos(2 pi (ph-4)/16)
   }
-  st<DT>(out, ob + k, re);
-  st<DT>(out, ob + 9 + k, im);
+  store_as<DT>(out, ob + k, re);
+  store_as<DT>(out, ob + 9 + k, im);
 }
 
 // ---- iSTFT: block = 64 frames -> 256 output samples; frames (+3 halo before) staged in LDS as real/imag
@@ -222,18 +216,12 @@ __global__ __launch_bounds__(256) void source_synth_kernel(const float* f0, cons
 
 }  // namespace
 
-#define DISPATCH_DT(dt, CALL)                                   \
-  switch (dt) {                                                 \
-    case CV_F32: { constexpr int DT = CV_F32; CALL; } break;    \
-    case CV_BF16: { constexpr int DT = CV_BF16; CALL; } break;  \
-    case CV_F16: { constexpr int DT = CV_F16; CALL; } break;    \
-    default: return CV_ERR_ARG;                                 \
-  }
-
 extern "C" int cv_to_channels_last(const float* x, void* out, int32_t dtype, int32_t B, int32_t C, int32_t T, int32_t ldo, void* stream) {
   if (!x || !out || B <= 0 || C <= 0 || T <= 0 || ldo < C) return CV_ERR_ARG;
   dim3 grid((T + 31) / 32, (ldo + 31) / 32, B);
-  DISPATCH_DT(dtype, hipLaunchKernelGGL(to_cl_kernel<DT>, grid, dim3(256), 0, (hipStream_t)stream, x, out, C, T, ldo));
+  if (!with_dt(dtype, [&](auto DT) {
+        hipLaunchKernelGGL(to_cl_kernel<DT()>, grid, dim3(256), 0, (hipStream_t)stream, x, out, C, T, ldo);
+      })) return CV_ERR_ARG;
   CV_CHECK_LAUNCH();
   return CV_OK;
 }
@@ -255,8 +243,9 @@ extern "C" int cv_snake_multi(const float* x, int32_t rows, int32_t C, int32_t l
   for (int i = 0; i < n; ++i) { a.alpha[i] = alpha[i]; a.out[i] = out[i]; if (!alpha[i] || !out[i]) return CV_ERR_ARG; }
   const int64_t n4 = (int64_t)rows * (C >> 2);
   const int blocks = (int)((n4 + 255) / 256 < 4096 ? (n4 + 255) / 256 : 4096);
-  if (dtype == CV_F32X3) hipLaunchKernelGGL(snake_multi_kernel<CV_F32X3>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, n4, C, ldx, n, ldo, a);
-  else DISPATCH_DT(dtype, hipLaunchKernelGGL(snake_multi_kernel<DT>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, n4, C, ldx, n, ldo, a));
+  if (!with_value<CV_F32, CV_BF16, CV_F16, CV_F32X3>(dtype, [&](auto DT) {
+        hipLaunchKernelGGL(snake_multi_kernel<DT()>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, n4, C, ldx, n, ldo, a);
+      })) return CV_ERR_ARG;
   CV_CHECK_LAUNCH();
   return CV_OK;
 }
@@ -265,7 +254,9 @@ extern "C" int cv_stft16(const float* s, void* out, int32_t dtype, int32_t B, in
   if (!s || !out || B <= 0 || S < 16 || (S & 3) || ldo < 18) return CV_ERR_ARG;
   const int F = S / 4 + 1;
   dim3 grid((F * 12 + 255) / 256, B);
-  DISPATCH_DT(dtype, hipLaunchKernelGGL(stft16_kernel<DT>, grid, dim3(256), 0, (hipStream_t)stream, s, out, S, F, ldo, (const int32_t*)nullptr, 0, 0));
+  if (!with_dt(dtype, [&](auto DT) {
+        hipLaunchKernelGGL(stft16_kernel<DT()>, grid, dim3(256), 0, (hipStream_t)stream, s, out, S, F, ldo, (const int32_t*)nullptr, 0, 0);
+      })) return CV_ERR_ARG;
   CV_CHECK_LAUNCH();
   return CV_OK;
 }
@@ -275,7 +266,9 @@ int hift_stft16_ragged(const float* s, void* out, int32_t dtype, int32_t B, int3
   if (!s || !out || !lens || B <= 0 || T <= 0 || S < 16 || (S % T) || ((S / T) & 3) || S / T < 16 || ldo < 18) return CV_ERR_ARG;
   const int F = S / 4 + 1;
   dim3 grid((F * 12 + 255) / 256, B);
-  DISPATCH_DT(dtype, hipLaunchKernelGGL(stft16_kernel<DT>, grid, dim3(256), 0, (hipStream_t)stream, s, out, S, F, ldo, lens, S / T, T));
+  if (!with_dt(dtype, [&](auto DT) {
+        hipLaunchKernelGGL(stft16_kernel<DT()>, grid, dim3(256), 0, (hipStream_t)stream, s, out, S, F, ldo, lens, S / T, T);
+      })) return CV_ERR_ARG;
   CV_CHECK_LAUNCH();
   return CV_OK;
 }

@@ -1,11 +1,10 @@
 // LLM decode-step kernels for gfx950: skinny MFMA GEMM over pre-packed weights (HBM-bound weight streaming),
 // RMSNorm with split-K slab reduction, RoPE + KV append, single-query GQA attention, on-device RAS sampling.
 #include "cv_device.h"
-#include <algorithm>
+#include "skinny_select.h"
 
 namespace {
 
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ uint4 nt_load16(const uint4* p) {
   const u32x4_t v = __builtin_nontemporal_load((const u32x4_t*)p);
   return make_uint4(v.x, v.y, v.z, v.w);
@@ -352,12 +351,11 @@ __global__ __launch_bounds__(256, ((TPW == 2 && (TPR >= 32 || (MR == 2 && RS))) 
 // paying one cold round trip per workgroup — what matters when the decode loop owns 64-96 CUs (tts_batches' CU partition:
 // 304 single-shot workgroups on 96 CUs ran as two full rounds, 11.2 us; see tools/llm_kernel_bench.py) and harmless with
 // one group per workgroup.  The norm prologue and the activation fragments are produced once per workgroup.
-// LOOP = false: one group per workgroup (grid = groups): no second register set, no dummy loads.
-template <int DT, int TPW, int NORM, int TPR, int U, bool LOOP>
+template <int DT, int TPW, int NORM, int TPR, int U>
 __global__ __launch_bounds__(256) void skinny_stream_kernel(const cv_skinny_params p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  float4 (*red)[4][TPW][64] = (float4 (*)[4][TPW][64])smem;            // [LOOP ? 2 : 1][4][TPW][64]
-  char* aimg = smem + (LOOP ? 2 : 1) * 4 * TPW * 64 * sizeof(float4);   // NORM: [nks][64 lanes][16 B]
+  float4 (*red)[4][TPW][64] = (float4 (*)[4][TPW][64])smem;            // [2][4][TPW][64]
+  char* aimg = smem + 2 * 4 * TPW * 64 * sizeof(float4);   // NORM: [nks][64 lanes][16 B]
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int nks = p.K >> 5;
   const int per = (nks + p.ksplit - 1) / p.ksplit;
@@ -534,10 +532,6 @@ __global__ __launch_bounds__(256) void skinny_stream_kernel(const cv_skinny_para
     ++it;
   };
 
-  if constexpr (!LOOP) {
-    compute(wA, rA, blockIdx.x);
-    return;
-  }
   for (int g = blockIdx.x; g < ngroups;) {
     load_group(wB, rB, g + stride);
     compute(wA, rA, g);
@@ -669,7 +663,6 @@ __global__ __launch_bounds__(256) void kv_retile_kernel(const uint16_t* k_rm, co
 }
 
 // =========================================================================================== decode attention
-constexpr float NEG_BIG = -1e30f;
 constexpr int DA_WAVES = 8;
 
 // One workgroup per (kv head, sequence); every wave owns key tiles wid, wid + 8 (64 keys each) and issues the loads of BOTH
@@ -679,7 +672,7 @@ constexpr int DA_WAVES = 8;
 // and loaded a wave's second tile only after finishing its first: two more dependent HBM round trips, 8.5 us per call.)
 // FUSED is a template parameter, not `qkv != nullptr` at run time: a run-time branch around the qkv loads ends in PHIs
 // with the zero defaults, and hipcc then waits for those loads before it issues the K/V tile loads.
-template <int DT, bool FUSED, int ABL = 0>   // ABL: timing-only ablations (results are wrong; instantiated by hand for a measurement, DESIGN.md §4 decode_attn_kernel row): 1 no MFMA/softmax, 2 no K/V loads
+template <int DT, bool FUSED>
 __global__ __launch_bounds__(512) void decode_attn_kernel(const uint16_t* q, int ldq, uint16_t* kcache, uint16_t* vtcache,
                                                           const int32_t* ctx_len, int ctx_add, uint16_t* out, int ldo, int Hq, int Hkv,
                                                           int ctx_max, float scale, const float* qkv, int ldqkv, const float* inv_freq) {
@@ -763,16 +756,7 @@ __global__ __launch_bounds__(512) void decode_attn_kernel(const uint16_t* q, int
   // The first tile of every wave (keys < 512) is fetched unconditionally — its addresses do not depend on `pos`, so the loads
   // leave with the qkv words instead of one L2 round trip later (tiles beyond the context are in bounds of the cache and are
   // simply not used); the second tile (contexts beyond 512 keys) waits for `pos`.
-  if constexpr (ABL == 2) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      kfA[i][0] = kfA[i][1] = kfB[i][0] = kfB[i][1] = make_uint4(0, 0, 0, 0);
-      vfA[i][0][0] = vfA[i][0][1] = vfA[i][1][0] = vfA[i][1][1] = make_uint2(0, 0);
-      vfB[i][0][0] = vfB[i][0][1] = vfB[i][1][0] = vfB[i][1][1] = make_uint2(0, 0);
-    }
-  } else {
-    load_tile(kfA, vfA, min(wid, (ctx_max >> 6) - 1));
-  }
+  load_tile(kfA, vfA, min(wid, (ctx_max >> 6) - 1));
   __builtin_amdgcn_sched_barrier(0);   // hipcc otherwise hoists the wait for `pos` above half of these loads
   const int pos = __builtin_amdgcn_readfirstlane(pos_v);
   const int ctx = min(pos + ctx_add, ctx_max);
@@ -783,7 +767,7 @@ __global__ __launch_bounds__(512) void decode_attn_kernel(const uint16_t* q, int
     s0 = *(const float4*)(cs_row + 32 + 8 * lg); s1 = *(const float4*)(cs_row + 32 + 8 * lg + 4);
     kcs = cs_row[lane & 31]; ksn = cs_row[32 + (lane & 31)];
   }
-  if (ABL != 2 && wid + DA_WAVES < ntiles) load_tile(kfB, vfB, wid + DA_WAVES);
+  if (wid + DA_WAVES < ntiles) load_tile(kfB, vfB, wid + DA_WAVES);
   if constexpr (FUSED) {
 #define ROPE_LO(x1, x2, c, s_) ((x1) * (c) - (x2) * (s_))
 #define ROPE_HI(x1, x2, c, s_) ((x2) * (c) + (x1) * (s_))
@@ -859,16 +843,6 @@ __global__ __launch_bounds__(512) void decode_attn_kernel(const uint16_t* q, int
             vf[dt][s2][h] = make_uint2(x0, x1);
           }
       }
-    }
-    if constexpr (ABL == 1) {   // keep the loads alive, skip the arithmetic
-      uint32_t acc_ = 0;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        acc_ ^= kf[i][0].x ^ kf[i][0].y ^ kf[i][0].z ^ kf[i][0].w ^ kf[i][1].x ^ kf[i][1].y ^ kf[i][1].z ^ kf[i][1].w;
-        acc_ ^= vf[i][0][0].x ^ vf[i][0][0].y ^ vf[i][0][1].x ^ vf[i][0][1].y ^ vf[i][1][0].x ^ vf[i][1][0].y ^ vf[i][1][1].x ^ vf[i][1][1].y;
-      }
-      oacc[0][0] += __uint_as_float(acc_ & 0x3F800000u);
-      return;
     }
     f32x4_t sacc[4];
 #pragma unroll
@@ -1278,13 +1252,6 @@ __global__ __launch_bounds__(256) void sample_kernel(const cv_sample_params p) {
 
 }  // namespace
 
-#define DISPATCH_16(dt, CALL)                                   \
-  switch (dt) {                                                 \
-    case CV_BF16: { constexpr int DT = CV_BF16; CALL; } break;  \
-    case CV_F16: { constexpr int DT = CV_F16; CALL; } break;    \
-    default: return CV_ERR_UNSUPPORTED;                         \
-  }
-
 extern "C" int cv_sizeof_skinny_params(void) { return (int)sizeof(cv_skinny_params); }
 extern "C" int cv_sizeof_sample_params(void) { return (int)sizeof(cv_sample_params); }
 
@@ -1293,126 +1260,37 @@ extern "C" int cv_pack_skinny(const void* W, void* Wp, int32_t N, int32_t K, int
   if (interleave && (N & 31)) return CV_ERR_ARG;
   const int ntiles = (N + 15) / 16;
   const int64_t total = (int64_t)ntiles * (K >> 5) * 64;
-  const int blocks = (int)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
-  hipLaunchKernelGGL(pack_skinny_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)W, (uint16_t*)Wp, N, K,
+  hipLaunchKernelGGL(pack_skinny_kernel, dim3(blocks_of_256(total)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)W, (uint16_t*)Wp, N, K,
                      ntiles, interleave);
   CV_CHECK_LAUNCH();
   return CV_OK;
 }
 
+namespace {
+// SkinnySel -> the one template instantiation it names (skinny_built: the forms that exist; nothing else is instantiated)
+typedef void (*skinny_fn)(const cv_skinny_params);
+template <int DT>
+skinny_fn skinny_form(const SkinnySel& s) {
+  skinny_fn k = nullptr;
+  with_value<1, 2>(s.tpw, [&](auto TPW) { with_value<0, 1, 2, 3, 5>(s.norm, [&](auto NORM) { with_value<16, 32, 64>(s.tpr, [&](auto TPR) {
+  with_value<7, 8, 10, 12, 16>(s.u, [&](auto U) { with_value<0, 1>(s.rs, [&](auto RS) { with_value<1, 2>(s.mr, [&](auto MR) {
+    if constexpr (skinny_built(true, TPW(), NORM(), TPR(), U(), RS(), MR()))
+      if (s.stream) k = skinny_stream_kernel<DT, TPW(), NORM(), TPR(), U()>;
+    if constexpr (skinny_built(false, TPW(), NORM(), TPR(), U(), RS(), MR()))
+      if (!s.stream) k = skinny_kernel<DT, TPW(), NORM(), TPR(), U(), RS() != 0, MR()>;
+  }); }); }); }); }); });
+  return k;
+}
+}  // namespace
+
 extern "C" int cv_skinny_gemm(const cv_skinny_params* pp, void* stream) {
   if (!pp) return CV_ERR_ARG;
   cv_skinny_params p = *pp;
-  const bool norm = p.ngamma != nullptr;
-  if (p.M <= 0 || p.M > 32 || p.N <= 0 || p.K <= 0 || (p.K & 31) || !p.Wp) return CV_ERR_ARG;
-  if (p.M > 16 && (norm || p.mode == 3)) return CV_ERR_UNSUPPORTED;   // two row groups: plain-row forms of modes 0 / 1 / 2 only
-  if (!norm && (!p.A || (p.lda & 7))) return CV_ERR_ARG;
-  if (norm) {
-    if (!p.nx || (p.K & 63) || p.K > 1024 || (p.ldnx & 3) || p.nx_out == p.nx) return CV_ERR_ARG;
-    if (p.n_nslab > 0 && (!p.nslabs || (p.ld_nslab & 3) || (p.nslab_stride & 3))) return CV_ERR_ARG;
-    if (p.n_nslab != 0 && p.n_nslab != 1 && p.n_nslab != 2 && p.n_nslab != 4) return CV_ERR_ARG;
-  }
-  if (p.ksplit <= 0) p.ksplit = 1;
-  const int ntiles = (p.N + 15) / 16;
-  hipStream_t st = (hipStream_t)stream;
-  const size_t img = norm ? (size_t)(p.K >> 5) * 1024 : 0;
-  const int nm = !norm ? 0 : 1 + p.n_nslab;
-  const int tpr = p.M <= 4 ? 64 : (p.M <= 8 ? 32 : 16);
-  const int tpw = p.mode == 2 ? 2 : 1;
-  if (p.mode == 2) {
-    if (p.ksplit != 1 || (ntiles & 1) || !p.out_act || (p.ldoa & 3)) return CV_ERR_ARG;
-    if (p.rs_part) {
-      if (norm || p.n_rs_part <= 0 || p.n_rs_part > 64) return CV_ERR_ARG;
-      p.max_wgs = 0;
-    }
-  } else if (p.mode == 3) {
-    if (p.ksplit != 1 || !p.out_act || norm) return CV_ERR_ARG;
-    p.max_wgs = 0;   // single-shot kernel only
-  } else if (p.mode == 1 && (p.xb_out || p.ss_part)) {
-    if (!p.out_f32 || p.ksplit != 1 || !p.xb_out || !p.ss_part || p.ldxb < p.N) return CV_ERR_ARG;
-    p.max_wgs = 0;
-  } else {
-    if (!p.out_f32) return CV_ERR_ARG;
-    if (p.mode == 1 && p.ksplit != 1) return CV_ERR_ARG;
-  }
-  // k-steps one wave covers: the streaming kernel takes them as one batch of U fragment loads
-  const int per_wave = ((((p.K >> 5) + p.ksplit - 1) / p.ksplit) + 3) >> 2;
-  const int ngroups = ntiles / tpw;
-  if (p.mode == 2 && p.rs_part && per_wave > 8) return CV_ERR_UNSUPPORTED;   // split-norm consumer: K <= 1024 only
-  if (p.M > 16) {   // 17..32 rows: two 16-row groups share every weight fragment (MR = 2); single-shot workgroups
-    dim3 grid(ngroups, p.ksplit);
-    const size_t lds = 2 * 4 * tpw * 64 * 4 * sizeof(float);
-    const bool exact7 = per_wave == 7 && ((p.K >> 5) == 28 * p.ksplit);
-    if (tpw == 2) {
-      if (!p.rs_part) return CV_ERR_UNSUPPORTED;
-      // (two (gate, up) tile pairs per workgroup — skinny_kernel<DT, 4, 0, 16, 7, true, 2>, half the activation traffic — was measured at
-      // 19.9 vs 20.7 us on 64 CUs and 10.8 vs 10.4 us on all: at 240 VGPRs its 152 workgroups still need two rounds; not dispatched)
-      if (exact7) { DISPATCH_16(p.dtype, hipLaunchKernelGGL((skinny_kernel<DT, 2, 0, 16, 7, true, 2>), grid, dim3(256), lds, st, p)); }
-      else { DISPATCH_16(p.dtype, hipLaunchKernelGGL((skinny_kernel<DT, 2, 0, 16, 8, true, 2>), grid, dim3(256), lds, st, p)); }
-    } else if (per_wave > 8 && per_wave <= 10 && !(ntiles & 1)) {
-      // long-K form (the down projection): with two row groups the activation slice a workgroup reads (32 rows x its K range) is twice
-      // its weight tile, so two weight tiles share it (TPW = 2: half the workgroups, half the activation traffic)
-      dim3 grid2(ngroups / 2, p.ksplit);
-      const size_t lds2 = 2 * 4 * 2 * 64 * 4 * sizeof(float);
-      DISPATCH_16(p.dtype, hipLaunchKernelGGL((skinny_kernel<DT, 2, 0, 16, 10, false, 2>), grid2, dim3(256), lds2, st, p));
-    } else if (exact7) { DISPATCH_16(p.dtype, hipLaunchKernelGGL((skinny_kernel<DT, 1, 0, 16, 7, false, 2>), grid, dim3(256), lds, st, p)); }
-    else if (per_wave <= 8) { DISPATCH_16(p.dtype, hipLaunchKernelGGL((skinny_kernel<DT, 1, 0, 16, 8, false, 2>), grid, dim3(256), lds, st, p)); }
-    else if (per_wave <= 12) { DISPATCH_16(p.dtype, hipLaunchKernelGGL((skinny_kernel<DT, 1, 0, 16, 12, false, 2>), grid, dim3(256), lds, st, p)); }
-    else { DISPATCH_16(p.dtype, hipLaunchKernelGGL((skinny_kernel<DT, 1, 0, 16, 16, false, 2>), grid, dim3(256), lds, st, p)); }
-    CV_CHECK_LAUNCH();
-    return CV_OK;
-  }
-  if (per_wave > 16 || (tpw == 2 && per_wave > 8)) {
-    if (norm) return CV_ERR_UNSUPPORTED;  // cannot happen: the prologue needs K <= 1024
-    dim3 grid(ngroups, p.ksplit);
-    const size_t lds = 4 * tpw * 64 * 4 * sizeof(float);
-    if (tpw == 2) { DISPATCH_16(p.dtype, hipLaunchKernelGGL((skinny_kernel<DT, 2, 0, 16, 8>), grid, dim3(256), lds, st, p)); }
-    else { DISPATCH_16(p.dtype, hipLaunchKernelGGL((skinny_kernel<DT, 1, 0, 16, 8>), grid, dim3(256), lds, st, p)); }
-    CV_CHECK_LAUNCH();
-    return CV_OK;
-  }
-  int gx = ngroups;
-  if (p.max_wgs > 0) gx = std::min(ngroups, std::max(1, p.max_wgs / p.ksplit));
-  dim3 grid(gx, p.ksplit);
-  const bool loop = gx < ngroups;
-  const size_t lds = (loop ? 2 : 1) * 4 * tpw * 64 * 4 * sizeof(float) + img;
-  // every wave's K slice is exactly 7 k-steps (K = 896 * ksplit): single-shot launches use the clamp-free U = 7 form
-  const bool exact7 = !loop && per_wave == 7 && ((p.K >> 5) == 28 * p.ksplit);
-#define SK_LAUNCH7(TPW_, NM_, TPR_) \
-  DISPATCH_16(p.dtype, hipLaunchKernelGGL((skinny_kernel<DT, TPW_, NM_, TPR_, 7>), grid, dim3(256), lds, st, p))
-#define SK_LAUNCH(TPW_, NM_, TPR_, U_)                                                                                          \
-  do {                                                                                                                          \
-    if (loop) { DISPATCH_16(p.dtype, hipLaunchKernelGGL((skinny_stream_kernel<DT, TPW_, NM_, TPR_, U_, true>), grid, dim3(256), lds, st, p)); } \
-    else { DISPATCH_16(p.dtype, hipLaunchKernelGGL((skinny_kernel<DT, TPW_, NM_, TPR_, U_>), grid, dim3(256), lds, st, p)); }                   \
-  } while (0)
-#define SK_TPR(TPW_, NM_)                                                                                                  \
-  do {                                                                                                                     \
-    if (tpr == 64) { SK_LAUNCH(TPW_, NM_, 64, 8); }                                                                        \
-    else if (tpr == 32) { if (exact7) { SK_LAUNCH7(TPW_, NM_, 32); } else { SK_LAUNCH(TPW_, NM_, 32, 8); } }               \
-    else { if (exact7) { SK_LAUNCH7(TPW_, NM_, 16); } else { SK_LAUNCH(TPW_, NM_, 16, 8); } }                               \
-  } while (0)
-#define SK_NORM(TPW_)                          \
-  do {                                         \
-    if (nm == 1) { SK_TPR(TPW_, 1); }          \
-    else if (nm == 2) { SK_TPR(TPW_, 2); }     \
-    else if (nm == 3) { SK_TPR(TPW_, 3); }     \
-    else { SK_TPR(TPW_, 5); }                  \
-  } while (0)
-  if (tpw == 2) {
-    if (nm == 0 && p.rs_part) {
-      if (exact7) { DISPATCH_16(p.dtype, hipLaunchKernelGGL((skinny_kernel<DT, 2, 0, 16, 7, true>), grid, dim3(256), lds, st, p)); }
-      else { DISPATCH_16(p.dtype, hipLaunchKernelGGL((skinny_kernel<DT, 2, 0, 16, 8, true>), grid, dim3(256), lds, st, p)); }
-    } else if (nm == 0) { SK_LAUNCH(2, 0, 16, 8); } else { SK_NORM(2); }
-  } else if (nm == 0) {
-    if (exact7) { SK_LAUNCH7(1, 0, 16); }
-    else if (per_wave <= 8) { SK_LAUNCH(1, 0, 16, 8); } else if (per_wave <= 12) { SK_LAUNCH(1, 0, 16, 12); } else { SK_LAUNCH(1, 0, 16, 16); }
-  } else {
-    SK_NORM(1);
-  }
-#undef SK_NORM
-#undef SK_TPR
-#undef SK_LAUNCH7
-#undef SK_LAUNCH
+  SkinnySel s;
+  if (int rc = skinny_select(p, &s)) return rc;
+  skinny_fn k = nullptr;
+  if (!with_dt16(p.dtype, [&](auto DT) { k = skinny_form<DT()>(s); }) || !k) return CV_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(k, dim3(s.grid_x, s.grid_y), dim3(256), s.lds, (hipStream_t)stream, p);
   CV_CHECK_LAUNCH();
   return CV_OK;
 }
@@ -1422,12 +1300,9 @@ extern "C" int cv_rmsnorm_reduce(float* x, int32_t ldx, const float* slabs, int3
   if (!x || !gamma || !xn || rows <= 0 || dim <= 0 || (dim & 3) || dim > 4096 || (ldx & 3) || (ldxn & 3)) return CV_ERR_ARG;
   if (nslab > 0 && (!slabs || (ld_slab & 3) || (slab_stride & 3))) return CV_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
-  switch (dtype) {
-    case CV_F32: hipLaunchKernelGGL(rmsnorm_reduce_kernel<CV_F32>, dim3(rows), dim3(256), 0, st, x, ldx, slabs, nslab, slab_stride, ld_slab, gamma, eps, xn, ldxn, dim); break;
-    case CV_BF16: hipLaunchKernelGGL(rmsnorm_reduce_kernel<CV_BF16>, dim3(rows), dim3(256), 0, st, x, ldx, slabs, nslab, slab_stride, ld_slab, gamma, eps, xn, ldxn, dim); break;
-    case CV_F16: hipLaunchKernelGGL(rmsnorm_reduce_kernel<CV_F16>, dim3(rows), dim3(256), 0, st, x, ldx, slabs, nslab, slab_stride, ld_slab, gamma, eps, xn, ldxn, dim); break;
-    default: return CV_ERR_ARG;
-  }
+  if (!with_dt(dtype, [&](auto DT) {
+        hipLaunchKernelGGL(rmsnorm_reduce_kernel<DT()>, dim3(rows), dim3(256), 0, st, x, ldx, slabs, nslab, slab_stride, ld_slab, gamma, eps, xn, ldxn, dim);
+      })) return CV_ERR_ARG;
   CV_CHECK_LAUNCH();
   return CV_OK;
 }
@@ -1451,11 +1326,9 @@ extern "C" int cv_relpos_append(const float* qkv, void* qq, void* kcache, void* 
                                 int32_t vt_ld, void* stream) {
   if (!qkv || !qq || !kcache || !vtcache || D <= 0 || t < 0 || t >= vt_ld) return CV_ERR_ARG;
   dim3 grid((4 * D + 255) / 256);
-  switch (dtype) {
-    case CV_BF16: hipLaunchKernelGGL(relpos_append_kernel<CV_BF16>, grid, dim3(256), 0, (hipStream_t)stream, qkv, qq, kcache, vtcache, D, t, vt_ld); break;
-    case CV_F16: hipLaunchKernelGGL(relpos_append_kernel<CV_F16>, grid, dim3(256), 0, (hipStream_t)stream, qkv, qq, kcache, vtcache, D, t, vt_ld); break;
-    default: return CV_ERR_ARG;
-  }
+  if (!with_dt16(dtype, [&](auto DT) {
+        hipLaunchKernelGGL(relpos_append_kernel<DT()>, grid, dim3(256), 0, (hipStream_t)stream, qkv, qq, kcache, vtcache, D, t, vt_ld);
+      })) return CV_ERR_ARG;
   CV_CHECK_LAUNCH();
   return CV_OK;
 }
@@ -1464,8 +1337,10 @@ extern "C" int cv_rope_append(const float* qkv, int32_t ldqkv, const int32_t* po
                               int32_t Hq, int32_t Hkv, const float* inv_freq, void* q_out, int32_t ldq, void* kcache, void* vtcache,
                               int32_t ctx_max, int32_t dtype, void* stream) {
   if (!qkv || !pos_base || !inv_freq || !q_out || !kcache || !vtcache || rows <= 0 || rows_per_seq <= 0 || Hq <= 0 || Hkv <= 0) return CV_ERR_ARG;
-  DISPATCH_16(dtype, hipLaunchKernelGGL(rope_append_kernel<DT>, dim3(rows), dim3(256), 0, (hipStream_t)stream, qkv, ldqkv, pos_base,
-                                        rows_per_seq, Hq, Hkv, inv_freq, (uint16_t*)q_out, ldq, (uint16_t*)kcache, (uint16_t*)vtcache, ctx_max));
+  if (!with_dt16(dtype, [&](auto DT) {
+        hipLaunchKernelGGL(rope_append_kernel<DT()>, dim3(rows), dim3(256), 0, (hipStream_t)stream, qkv, ldqkv, pos_base, rows_per_seq, Hq,
+                           Hkv, inv_freq, (uint16_t*)q_out, ldq, (uint16_t*)kcache, (uint16_t*)vtcache, ctx_max);
+      })) return CV_ERR_UNSUPPORTED;
   CV_CHECK_LAUNCH();
   return CV_OK;
 }
@@ -1490,16 +1365,11 @@ extern "C" int cv_decode_attention(const void* q, int32_t ldq, const void* kcach
   if (!qkv && (!q || (ldq & 7))) return CV_ERR_ARG;
   if (qkv && (!inv_freq || ldqkv < (Hq + 2 * Hkv) * 64)) return CV_ERR_ARG;
   if ((ldo & 3) || (ctx_max & 63)) return CV_ERR_ARG;
-  dim3 grid(Hkv, B);
-  if (qkv) {
-    DISPATCH_16(dtype, hipLaunchKernelGGL((decode_attn_kernel<DT, true>), grid, dim3(512), 0, (hipStream_t)stream, (const uint16_t*)q, ldq,
-                                          (uint16_t*)kcache, (uint16_t*)vtcache, ctx_len, ctx_add, (uint16_t*)out, ldo, Hq, Hkv,
-                                          ctx_max, scale, qkv, ldqkv, inv_freq));
-  } else {
-    DISPATCH_16(dtype, hipLaunchKernelGGL((decode_attn_kernel<DT, false>), grid, dim3(512), 0, (hipStream_t)stream, (const uint16_t*)q, ldq,
-                                          (uint16_t*)kcache, (uint16_t*)vtcache, ctx_len, ctx_add, (uint16_t*)out, ldo, Hq, Hkv,
-                                          ctx_max, scale, qkv, ldqkv, inv_freq));
-  }
+  // FUSED is a template argument (see decode_attn_kernel), so the kernel is picked first and launched once
+  void (*k)(const uint16_t*, int, uint16_t*, uint16_t*, const int32_t*, int, uint16_t*, int, int, int, int, float, const float*, int, const float*) = nullptr;
+  if (!with_dt16(dtype, [&](auto DT) { k = qkv ? decode_attn_kernel<DT(), true> : decode_attn_kernel<DT(), false>; })) return CV_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(k, dim3(Hkv, B), dim3(512), 0, (hipStream_t)stream, (const uint16_t*)q, ldq, (uint16_t*)kcache, (uint16_t*)vtcache, ctx_len,
+                     ctx_add, (uint16_t*)out, ldo, Hq, Hkv, ctx_max, scale, qkv, ldqkv, inv_freq);
   CV_CHECK_LAUNCH();
   return CV_OK;
 }

@@ -108,17 +108,6 @@ __global__ __launch_bounds__(EXPAND_THREADS) void lora_expand_kernel(const cv_lo
   *y = p.mode == CV_LORA_STORE ? d : *y + d;
 }
 
-template <int DT>
-int launch_expand(const cv_lora_expand_params& p, dim3 grid, hipStream_t st) {
-  switch (p.r) {
-    case 8: hipLaunchKernelGGL((lora_expand_kernel<DT, 8>), grid, dim3(EXPAND_THREADS), 0, st, p); break;
-    case 16: hipLaunchKernelGGL((lora_expand_kernel<DT, 16>), grid, dim3(EXPAND_THREADS), 0, st, p); break;
-    default: hipLaunchKernelGGL((lora_expand_kernel<DT, 32>), grid, dim3(EXPAND_THREADS), 0, st, p); break;
-  }
-  CV_CHECK_LAUNCH();
-  return CV_OK;
-}
-
 }  // namespace
 
 extern "C" int cv_sizeof_lora_shrink_params(void) { return (int)sizeof(cv_lora_shrink_params); }
@@ -135,8 +124,7 @@ extern "C" int cv_lora_shrink(const cv_lora_shrink_params* pp, void* stream) {
   if (!aligned_to(p.x, 16) || !aligned_to(p.A, 16) || !aligned_to(p.row_adapter, 4) || !aligned_to(p.u, 4)) return CV_ERR_ARG;
   if (p.rows > 65535) return CV_ERR_UNSUPPORTED;               // grid.y
   const dim3 grid((p.R_tot + SHRINK_JB - 1) / SHRINK_JB, p.rows);
-  if (p.dtype == CV_BF16) hipLaunchKernelGGL(lora_shrink_kernel<CV_BF16>, grid, dim3(SHRINK_WAVES * 64), 0, (hipStream_t)stream, p);
-  else hipLaunchKernelGGL(lora_shrink_kernel<CV_F16>, grid, dim3(SHRINK_WAVES * 64), 0, (hipStream_t)stream, p);
+  with_dt16(p.dtype, [&](auto DT) { hipLaunchKernelGGL(lora_shrink_kernel<DT()>, grid, dim3(SHRINK_WAVES * 64), 0, (hipStream_t)stream, p); });
   CV_CHECK_LAUNCH();
   return CV_OK;
 }
@@ -170,5 +158,11 @@ extern "C" int cv_lora_expand(const cv_lora_expand_params* pp, void* stream) {
   }
   if (p.rows > 65535) return CV_ERR_UNSUPPORTED;               // grid.y
   const dim3 grid((cols + EXPAND_THREADS - 1) / EXPAND_THREADS, p.rows);
-  return p.dtype == CV_BF16 ? launch_expand<CV_BF16>(p, grid, (hipStream_t)stream) : launch_expand<CV_F16>(p, grid, (hipStream_t)stream);
+  with_dt16(p.dtype, [&](auto DT) {
+    with_value<8, 16, 32>(p.r, [&](auto R) {
+      hipLaunchKernelGGL((lora_expand_kernel<DT(), R()>), grid, dim3(EXPAND_THREADS), 0, (hipStream_t)stream, p);
+    });
+  });
+  CV_CHECK_LAUNCH();
+  return CV_OK;
 }

@@ -184,12 +184,8 @@ extern "C" int cv_groupnorm_cl(const cv_groupnorm_params* pp, void* stream) {
   dim3 grid((p.T + GN_ROWS - 1) / GN_ROWS, p.groups, p.B);
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(gn_stats_kernel, grid, dim3(256), 0, st, p);
-  switch (p.out_act ? p.out_dtype : CV_F32) {
-    case CV_F32: hipLaunchKernelGGL(gn_apply_kernel<CV_F32>, grid, dim3(256), 0, st, p); break;
-    case CV_BF16: hipLaunchKernelGGL(gn_apply_kernel<CV_BF16>, grid, dim3(256), 0, st, p); break;
-    case CV_F16: hipLaunchKernelGGL(gn_apply_kernel<CV_F16>, grid, dim3(256), 0, st, p); break;
-    default: return CV_ERR_ARG;
-  }
+  if (!with_dt(p.out_act ? p.out_dtype : CV_F32, [&](auto DT) { hipLaunchKernelGGL(gn_apply_kernel<DT()>, grid, dim3(256), 0, st, p); }))
+    return CV_ERR_ARG;
   CV_CHECK_LAUNCH();
   return CV_OK;
 }
@@ -205,20 +201,10 @@ extern "C" int cv_layernorm(const cv_norm_params* pp, void* stream) {
   if (p.rows_per_group <= 0) p.rows_per_group = p.rows;
   dim3 grid((p.rows + 3) / 4);
   hipStream_t st = (hipStream_t)stream;
-#define NORM_LAUNCH(ODT_)                                                                                    \
-  do {                                                                                                       \
-    if (p.dim <= 256) hipLaunchKernelGGL((norm_kernel<ODT_, 1>), grid, dim3(256), 0, st, p);                  \
-    else if (p.dim <= 512) hipLaunchKernelGGL((norm_kernel<ODT_, 2>), grid, dim3(256), 0, st, p);             \
-    else if (p.dim <= 1024) hipLaunchKernelGGL((norm_kernel<ODT_, 4>), grid, dim3(256), 0, st, p);            \
-    else hipLaunchKernelGGL((norm_kernel<ODT_, 8>), grid, dim3(256), 0, st, p);                               \
-  } while (0)
-  switch (p.out_dtype) {
-    case CV_F32: NORM_LAUNCH(CV_F32); break;
-    case CV_BF16: NORM_LAUNCH(CV_BF16); break;
-    case CV_F16: NORM_LAUNCH(CV_F16); break;
-    default: return CV_ERR_ARG;
-  }
-#undef NORM_LAUNCH
+  const int nv = p.dim <= 256 ? 1 : (p.dim <= 512 ? 2 : (p.dim <= 1024 ? 4 : 8));   // float4 per lane
+  if (!with_dt(p.out_dtype, [&](auto ODT) {
+        with_value<1, 2, 4, 8>(nv, [&](auto NV) { hipLaunchKernelGGL((norm_kernel<ODT(), NV()>), grid, dim3(256), 0, st, p); });
+      })) return CV_ERR_ARG;
   CV_CHECK_LAUNCH();
   return CV_OK;
 }
